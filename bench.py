@@ -30,6 +30,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -215,12 +216,14 @@ def measure(cfg, device, B, N, steps, warmup, spinup, dist, rank, world, modes=4
     x0 = E.InitialDraw(prior, B, device)
     ev = L.HipEvents()
     loss.timing_events = ev
+    last = {}  # the arrays of the latest pass (kept on the device; only the last timed pass is read back, by --dump-outputs)
 
     def one_pass():
         """simulate + terminal cost + log-Z / ESS reduction (+ all-gather), all enqueued on the stream; the 36-byte
         result is read back by .result() -- after the timed region for all but the last pass, so that consecutive
         passes run back to back (a sampler in production does not idle the GPU between batches either)."""
-        _, rnd, _ = loss.simulate(ts, x0, *args, **kw)
+        x, rnd, _ = loss.simulate(ts, x0, *args, **kw)
+        last.update(x=x, rnd=rnd)
         return parallel.global_results_async(rnd, dist)
 
     if dist is not None:  # create the RCCL communicator now (~20 ms the first time): an idle gap right before the timed
@@ -247,6 +250,7 @@ def measure(cfg, device, B, N, steps, warmup, spinup, dist, rank, world, modes=4
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     results = [p.result() for p in pending]  # every pass produced its estimators
+    outputs = dict(last)  # the last timed pass: before the kernel-timing passes below replace it
     assert all(math.isfinite(r["log_norm_const_is"]) for r in results)
     if dist is not None:
         wt = torch.tensor([wall], device=device)
@@ -264,7 +268,38 @@ def measure(cfg, device, B, N, steps, warmup, spinup, dist, rank, world, modes=4
     hx, hrnd, _ = loss.simulate(ts, E.InitialDraw(prior, Z_BLOCK, device), *args, **kw)
     torch.cuda.synchronize()
     return dict(cfg=cfg, B=B, N=N, info=info, ts=ts, wall=wall, steps=steps, value=world * B * N * steps / wall, ms_per_step=1e3 * wall / steps,
-                kernel_ms=k_ms, res=results[-1], hip_block=(hx, hrnd), seed=1)
+                kernel_ms=k_ms, res=results[-1], hip_block=(hx, hrnd), seed=1, outputs=outputs)
+
+
+DUMP_ROWS = 16384              # particles of the fixed sample dumped for the secondary workloads
+HEAD_DUMP_BYTES = 40 << 20     # the headline's x_N and rnd are dumped whole up to this size (BASELINE size: 32 MB), else sampled
+
+
+def dump_outputs(out_dir, measured):
+    """--dump-outputs: what the timed path returned in its last timed pass (rank 0's shard), one .npy per array.  The headline
+    workload is written whole at its BASELINE size (x_N [B, d] float32, rnd [B] float32); the secondary workloads, and a headline
+    larger than HEAD_DUMP_BYTES, as a fixed sample of particles (indices from a seeded generator, written next to them as
+    <cfg>_sample_index), so that a whole dump stays under 64 MB.  The log-Z / ESS estimators of that pass
+    are written as float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for i, m in enumerate(measured):
+        cfg, x, rnd = m["cfg"], m["outputs"]["x"], m["outputs"]["rnd"].reshape(-1)
+        rows = DUMP_ROWS if i > 0 else max(DUMP_ROWS, HEAD_DUMP_BYTES // (4 * (x.shape[1] + 1)))
+        if x.shape[0] > rows:
+            idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+            files[f"{cfg}_sample_index"] = idx.double().numpy()
+            x, rnd = x[idx.to(x.device)], rnd[idx.to(rnd.device)]
+        files[f"{cfg}_x"] = x.detach().float().cpu().numpy()
+        files[f"{cfg}_rnd"] = rnd.detach().float().cpu().numpy()
+        keys = ("log_norm_const_is", "elbo", "ess", "lv_loss")
+        files[f"{cfg}_estimators"] = np.array([m["res"][k] for k in keys], dtype=np.float64)
+    total = sum(a.nbytes for a in files.values())
+    assert total <= 64 << 20, f"output dump of {total} bytes exceeds 64 MB"
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in files), "bytes": total,
+            "estimators": "log_norm_const_is, elbo, ess, lv_loss"}
 
 
 def path_of(cfg, info):
@@ -312,6 +347,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--spinup", type=float, default=0.3, help="seconds of untimed passes before the warm-up (clock ramp)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed pass returned (x_N, rnd, estimators) as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -361,6 +398,8 @@ def main():
             out["speedup_vs_cpu"] = e["speedup_vs_cpu"]
         if others:
             out["other_configs"] = [config_entry(m, 8.0, chunks[m["cfg"]], with_cpu) for m in others]
+        if a.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(a.dump_outputs, [head] + others)
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -952,8 +952,30 @@ def case_sampler(name, kind, seed, B=32, d=3, n_levels=5, n_warm=4, n_steps=3, p
     save(name, meta, arrays)
 
 
+def case_reference_objects_coef(name, d=16, K=3, N=8):
+    """The per-step coefficient table the drop-in EIReferenceSDELoss compiles from the REFERENCE's own objects: its VP, a ClippedCtrl
+    around its FourierMLP and a bound RDS.reference_ctrl (tests/test_host_cpu.py::test_reference_objects_compile_to_descriptors)."""
+    from sde_sampler_lrds_amd.losses import oc
+    r_sde = r_sdes.VP(diff_coeff_sq_min=0.1, diff_coeff_sq_max=10.0, scale_diff_coeff=1.0, terminal_t=1.0)
+    target = r_gauss.ManyModes(n_modes=K, dim=d, var=0.5, seed_loc=42, n_reference_samples=10)
+    net = r_mlp.FourierMLP(dim=d, activation=torch.nn.GELU(), num_layers=4, channels=64)
+
+    class FakeRDS:  # what solver/oc.py:563-592 leaves on the solver object
+        reference_distr_utils = dict(means_init=target.loc.clone(), variances_init=0.5 * torch.ones(K, d), weights_init=torch.ones(K))
+
+        def reference_ctrl(self, t, x):
+            return r_sde.marginal_gmm_score(t=t, x=x, **self.reference_distr_utils)
+
+    ctrl = r_rep.ClippedCtrl(base_model=net, clip_model=1e4)
+    loss = oc.EIReferenceSDELoss(ctrl, ctrl, sde=r_sde, method="lv", reference_ctrl=FakeRDS().reference_ctrl)
+    ts = torch.linspace(0.0, 1.0, N + 1)
+    save(name, dict(d=d, K=K, N=N, sde="vp", beta_min=0.1, beta_max=10.0, sigma=1.0, T=1.0),
+         dict(ts=ts, coef=loss._coef(ts, "cpu", with_ref=True)))
+
+
 CASES = {
     "unit_vectors": unit_vectors,
+    "reference_objects_coef": case_reference_objects_coef,
     # config 2 family (ManyModes d=128, RDS gmm-ref, VP, EI)
     "rds_ei_gmm_d128_k4": lambda n: case_rds_gmm(n, d=128, K=4, B=64, N=16, seed=11),
     "rds_ei_gmm_d128_k4_n256": lambda n: case_rds_gmm(n, d=128, K=4, B=32, N=256, seed=12),

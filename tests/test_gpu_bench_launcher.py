@@ -29,3 +29,28 @@ def test_bench_under_torch_distributed_run(gpu):
     assert j["roofline"]["bound"] in ("valu_issue", "mfma") and 0.0 < j["roofline"]["frac"] <= 1.0 and j["log_z_abs_err"] < 1e-3
     if j["roofline"]["bound"] == "valu_issue":
         assert j["roofline"]["traffic"] is not None and "library_digest" in j
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_reproducible(gpu, tmp_path):
+    """--dump-outputs writes the arrays of the last timed pass; two runs with the same arguments dump the same values (fixed seeds,
+    deterministic kernels), and --steps sets the number of timed passes."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--particles", "4096",
+               "--sde-steps", "32", "--no-cpu-baseline", "--no-other-configs", "--spinup", "0.05", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 2 and j["ms_per_step"] > 0.0
+        assert sorted(os.listdir(out)) == j["dumped_outputs"]["files"]
+        dumps.append({f: np.load(out / f) for f in j["dumped_outputs"]["files"]})
+    a, b = dumps
+    assert a["rds_gmm_x.npy"].shape == (4096, 128) and a["rds_gmm_rnd.npy"].shape == (4096,)
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f

@@ -266,32 +266,45 @@ def test_sampler_refusals_and_pairings():
         ebm_mle.smc_sampler(torch.zeros(3, 4, 2), t, None, 1, 1, st, per_noise_init=True, reweight_threshold=1.0)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/sde_sampler"), reason="the reference checkout only exists in the build container")
+def _foreign(obj):
+    """A stand-in for the reference's own object of the same class: an instance of a class with the same NAME, defined here, that
+    derives from none of this package's types (no isinstance test of the package can match it), with the same state and methods."""
+    cls, ns = type(obj), {}
+    for k in reversed(cls.__mro__):
+        if k.__module__.startswith("sde_sampler_lrds_amd"):
+            ns.update({n: v for n, v in vars(k).items() if n not in ("__dict__", "__weakref__")})
+    base = torch.nn.Module if isinstance(obj, torch.nn.Module) else object
+    new = type(cls.__name__, (base,), dict(ns, __module__="upstream", __qualname__=cls.__name__))
+    out = object.__new__(new)
+    out.__dict__.update(obj.__dict__)
+    return out
+
+
 def test_reference_objects_compile_to_descriptors():
     """INTEGRATION.md, route 1: the drop-in loss classes are handed the REFERENCE's own objects (its VP, ClippedCtrl / ScoreCtrl around
     its FourierMLP, its ManyModes / IsotropicGauss, a bound ``reference_ctrl`` with ``reference_distr_utils``).  Descriptor
-    compilation is host-side, so it is checked here: same coefficient table as with this package's classes, every object
-    recognised."""
-    import sys
-    import types
-    for n in ("wandb", "torchquad", "torchsde"):
-        sys.modules.setdefault(n, types.ModuleType(n))
-    sys.path.insert(0, "/root/reference")
-    try:
-        from sde_sampler.distr import gauss as r_gauss
-        from sde_sampler.eq import sdes as r_sdes
-        from sde_sampler.models import mlp as r_mlp
-        from sde_sampler.models import reparam as r_rep
-    finally:
-        sys.path.remove("/root/reference")
+    compilation is host-side, so it is checked here: same coefficient table as with this package's classes and as the reference's own
+    VP gave (tests/golden/reference_objects_coef.npz, gen_golden.py), every object recognised.  The reference's objects are stood in
+    for by objects of foreign classes with the reference's class names (``_foreign``): the engine recognises them by name and
+    attributes only."""
+    from sde_sampler_lrds_amd.distr import gauss as p_gauss
+    from sde_sampler_lrds_amd.eq import sdes as p_sdes
+    from sde_sampler_lrds_amd.models import mlp as p_mlp
+    from sde_sampler_lrds_amd.models import reparam as p_rep
+
+    def foreign_net(m):
+        f = _foreign(m)
+        f.timestep_embed = _foreign(m.timestep_embed)
+        return f
+    r_sde = _foreign(p_sdes.VP(0.1, 10.0, 1.0, terminal_t=1.0))
     from sde_sampler_lrds_amd.eq.sdes import VP
     from sde_sampler_lrds_amd.losses import oc
-    d, K = 16, 3
-    r_sde = r_sdes.VP(diff_coeff_sq_min=0.1, diff_coeff_sq_max=10.0, scale_diff_coeff=1.0, terminal_t=1.0)
-    target = r_gauss.ManyModes(n_modes=K, dim=d, var=0.5, seed_loc=42, n_reference_samples=10)
-    prior = r_gauss.IsotropicGauss(dim=d, scale=1.0)
-    net = r_mlp.FourierMLP(dim=d, activation=torch.nn.GELU(), num_layers=4, channels=64)
-    sm = r_mlp.TimeEmbed(dim_out=1, activation=torch.nn.GELU(), num_layers=4, channels=64)
+    fx = gc.load("reference_objects_coef")
+    d, K = fx.meta["d"], fx.meta["K"]
+    target = _foreign(p_gauss.ManyModes(n_modes=K, dim=d, var=0.5, seed_loc=42, n_reference_samples=10))
+    prior = _foreign(p_gauss.IsotropicGauss(dim=d, scale=1.0))
+    net = foreign_net(p_mlp.FourierMLP(dim=d, activation=torch.nn.GELU(), num_layers=4, channels=64))
+    sm = _foreign(p_mlp.TimeEmbed(dim_out=1, activation=torch.nn.GELU(), num_layers=4, channels=64))
 
     class FakeRDS:  # what solver/oc.py:563-592 leaves on the solver object
         reference_distr_utils = dict(means_init=target.loc.clone(), variances_init=0.5 * torch.ones(K, d), weights_init=torch.ones(K))
@@ -300,22 +313,24 @@ def test_reference_objects_compile_to_descriptors():
             return r_sde.marginal_gmm_score(t=t, x=x, **self.reference_distr_utils)
 
     rds = FakeRDS()
-    ts = torch.linspace(0.0, 1.0, 9)
+    ts = fx["ts"]
     keep = []
-    for ctrl in (r_rep.ClippedCtrl(base_model=net, clip_model=1e4),
-                 r_rep.ScoreCtrl(base_model=net, score_model=sm, target_score=target.score, detach_score=False, clip_score=1e4, clip_model=1e4),
-                 r_rep.LerpCtrl(base_model=net, score_model=sm, target_score=target.score, detach_score=False, clip_score=1e4, clip_model=1e4,
-                                sde=r_sde, prior_score=prior.score)):
+    for ctrl in (_foreign(p_rep.ClippedCtrl(base_model=net, clip_model=1e4)),
+                 _foreign(p_rep.ScoreCtrl(base_model=net, score_model=sm, target_score=target.score, detach_score=False, clip_score=1e4,
+                                          clip_model=1e4)),
+                 _foreign(p_rep.LerpCtrl(base_model=net, score_model=sm, target_score=target.score, detach_score=False, clip_score=1e4,
+                                         clip_model=1e4, sde=r_sde, prior_score=prior.score))):
         nd = E.net_desc(ctrl, "cpu", keep)
         assert nd.ctrl_kind == {"ClippedCtrl": L.CTRL_CLIPPED, "ScoreCtrl": L.CTRL_SCORE, "LerpCtrl": L.CTRL_LERP}[type(ctrl).__name__]
         tgt, lerp_prior = E.ctrl_target(ctrl)
         assert (tgt is None) == (nd.ctrl_kind == L.CTRL_CLIPPED) and (lerp_prior is not None) == (nd.ctrl_kind == L.CTRL_LERP)
-    ctrl = r_rep.ClippedCtrl(base_model=net, clip_model=1e4)
+    ctrl = _foreign(p_rep.ClippedCtrl(base_model=net, clip_model=1e4))
     loss = oc.EIReferenceSDELoss(ctrl, ctrl, sde=r_sde, method="lv", reference_ctrl=rds.reference_ctrl)
     kind, utils = E.resolve_reference(loss.reference_ctrl)
     assert kind == "gmm" and E.ref_desc(kind, utils, "cpu", keep).kind == L.REF_GMM_DIAG
     mine = oc.EIReferenceSDELoss(ctrl, ctrl, sde=VP(0.1, 10.0, 1.0, terminal_t=1.0), method="lv", reference_ctrl=rds.reference_ctrl)
     assert torch.equal(loss._coef(ts, "cpu", with_ref=True), mine._coef(ts, "cpu", with_ref=True))
+    assert torch.equal(mine._coef(ts, "cpu", with_ref=True), fx["coef"])
     res = E.resolve_logp(target.unnorm_log_prob)
     assert res is not None and E.dist_desc(res[0], "cpu", keep).kind == L.DIST_GMM_DIAG
     assert E.dist_desc(prior, "cpu", keep).kind == L.DIST_ISO_GAUSS
