@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SDENG_ABI_VERSION 3
+#define SDENG_ABI_VERSION 4
 
 /* error codes */
 #define SDENG_OK 0
@@ -75,7 +75,9 @@ extern "C" {
  *   [7]  score gain       score gain         1 - t/T      LerpCtrl: g(t); ScoreCtrl: 1
  *   [8]  lerp weight t/T  lerp weight        (unused)     LerpCtrl only
  *   [9]  s(tau)   [10] s(tau)^2*sigma_sq(tau)   [11] s(tau)^2   reference marginal (eq/sdes.py:228-229,247)
- *   [12..15] reserved
+ *   [12] sigma = sde_ctrl_noise   [13] p = sde_ctrl_dropout   [14] a_k = drift_coeff_t(tau_k)   [15] g_k = diff_coeff_t(tau_k)
+ *        LIN / EM with SDENG_FLAG_CTRL_NOISE / _DROPOUT only (else 0); tau_k = the time the loss hands its control (T - s for the RDS
+ *        losses and DIS-EI, s for DDS and TimeReversalLoss), with the reference's fp32 formulas of the loss's SDE (eq/sdes.py:143-148)
  * SDENG_FORM_EUBO (rows in iteration order): [0] t_net = T - s, [1] mean factor, [2] control gain (1, or 1/g with
  *   use_rescaling), [3] std factor, [4] running-cost weight (omega | dt g^2), [5] Ito weight (sqrt omega | std/mean),
  *   [6] <u,x> weight (0 | 1/mean - 1 + drift_coeff dt), [9..11] reference marginal at t_net.
@@ -97,6 +99,17 @@ extern "C" {
 #define SDENG_FLAG_REMOVE_REF 32u  /* RemoveReferenceCtrl(score, ref_score, use_rescaling=False) (models/reparam.py:46-64): the control the loss sees is
                                       ctrl(t, x) - ref_score(t, x), ref_score = the reference drift of `ref`.  Forward forms (LIN / EM) with a
                                       Score / Lerp / CancelDrift control and a diagonal reference; SDENG_E_UNSUPPORTED otherwise. */
+
+/* sde_ctrl_noise / sde_ctrl_dropout of log-variance training (BaseOCLoss.generative_and_sde_ctrl, losses/oc.py:97-102): the control that drives
+ * the step -- after the clip, the score / lerp terms and the FLAG_REMOVE_REF subtraction -- is perturbed before anything consumes it (running
+ * cost, update, Ito term; the reference writes it in place through the detached alias, so its value is the control of every term):
+ *   CTRL_NOISE    u += coef[12] * eps, eps = the Philox normals of stream 4 with the step noise's counter layout (particle0+p, feature/4, step, 4);
+ *   CTRL_DROPOUT  then u = -(coef[14] * x) / coef[15] wherever U > coef[13] (x: the state of the step), U = output word feature % 4 of
+ *                 Philox4x32-10 with counter (particle0+p, feature/4, step, 5), as ((bits>>9)+0.5)*2^-23.  `U > p` is the reference's
+ *                 convention (`rand_like > sde_ctrl_dropout`): an element is REPLACED with probability 1 - p.
+ * (Streams 2 and 3 belong to sdeng_langevin_moves.)  FORM_LIN / FORM_EM with a drift net; SDENG_E_UNSUPPORTED otherwise (CMCD, EUBO, Euler). */
+#define SDENG_FLAG_CTRL_NOISE 128u
+#define SDENG_FLAG_CTRL_DROPOUT 256u
 
 #define SDENG_FLAG_REUSE_PACK 64u  /* sdeng_ctrl_vjp only: the packed weight images of an earlier call with the same net are still in the
                                       workspace -- skip re-packing (a caller that walks the times one by one, e.g. an adjoint recursion) */

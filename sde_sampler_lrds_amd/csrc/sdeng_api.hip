@@ -492,6 +492,10 @@ extern "C" int sdeng_simulate(const sdeng_desc* d, void* stream) {
   if (d->form != SDENG_FORM_LIN && d->form != SDENG_FORM_EM && d->form != SDENG_FORM_CMCD && d->form != SDENG_FORM_EUBO &&
       d->form != SDENG_FORM_CMCD_EUBO)
     return fail(SDENG_E_INVALID, "unknown form %d", d->form);
+  if ((d->flags & (SDENG_FLAG_CTRL_NOISE | SDENG_FLAG_CTRL_DROPOUT)) &&
+      ((d->form != SDENG_FORM_LIN && d->form != SDENG_FORM_EM) || d->net.ctrl_kind == SDENG_CTRL_NONE))
+    return fail(SDENG_E_UNSUPPORTED, "FLAG_CTRL_NOISE / FLAG_CTRL_DROPOUT: forward forms (LIN / EM) with a drift net only (form %d, ctrl_kind %d)",
+                d->form, d->net.ctrl_kind);
   const int DT = tiles_of(d), dpad = 16 * DT;
   float* ws = static_cast<float*>(d->workspace);
 

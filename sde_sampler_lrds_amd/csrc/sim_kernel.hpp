@@ -78,6 +78,37 @@ SD_INLINE void add_ctrl_score_tile(const SimArgs& a, f32x4& u, const f32x4& sv, 
   }
 }
 
+// sde_ctrl_noise / sde_ctrl_dropout of log-variance training (BaseOCLoss.generative_and_sde_ctrl, losses/oc.py:97-102), on one feature tile of
+// the step's FINAL control (after the clip, the score / lerp terms and the RemoveReferenceCtrl subtraction), at the old state x:
+//   noise    u += sigma * eps                      eps: Philox normals of stream SD_CTRL_NOISE_STREAM, the step noise's counter layout
+//   dropout  u  = -(a_k x) / g_k  where  U > p     U: word feature % 4 of Philox stream SD_CTRL_DROPOUT_STREAM at the same counter
+// (noise first, then dropout overwrites: the reference's order; `rand > p` REPLACES an element with probability 1 - p, its convention).
+// coef[12..15] = sigma, p, a_k = drift_coeff_t(tau_k), g_k = diff_coeff_t(tau_k).  Each half is a wave-uniform test of its flag.  Pad
+// features (f >= d) keep their control (zero): their state carries noise, which -a x / g or sigma eps would leak into the running cost.
+// EXACT: NT = ceil(d / 16) (every kernel but the full-covariance ones, which may run with a tile more: feat_live's premise).
+#define SD_CTRL_NOISE_STREAM 4u    // (streams 2 and 3 are sdeng_langevin_moves')
+#define SD_CTRL_DROPOUT_STREAM 5u
+template <int NT, bool EXACT>
+SD_INLINE void perturb_ctrl_tile(const SimArgs& a, const float* cf, f32x4& u, const f32x4& x, uint32_t pidx, int k, int t, int g, int d) {
+  const uint32_t jb = static_cast<uint32_t>(4 * t + g);
+  f32x4 v = u;
+  if (a.flags & SDENG_FLAG_CTRL_NOISE) {
+    const float sigma = cf[12];
+    const f32x4 e = philox_normal4(pidx, static_cast<uint32_t>(k), jb, SD_CTRL_NOISE_STREAM, a.seed_lo, a.seed_hi);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = v[r] + sigma * e[r];  // (two roundings, like the reference's `sde_ctrl += noise * randn`)
+  }
+  if (a.flags & SDENG_FLAG_CTRL_DROPOUT) {
+    const float p = cf[13], ak = cf[14], gk = cf[15];
+    uint32_t bits[4];
+    philox4x32_10(pidx, jb, static_cast<uint32_t>(k), SD_CTRL_DROPOUT_STREAM, a.seed_lo, a.seed_hi, bits);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = u01(bits[r]) > p ? -((ak * x[r]) / gk) : v[r];  // -(sde.drift(t, x) / sde.diff(t, x)), OU
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) u[r] = (EXACT ? feat_live<NT>(t, r, 4 * g, d) : feat_lt(t, r, 4 * g, d)) ? v[r] : u[r];
+}
+
 // Waves per workgroup of an instantiation (one persistent workgroup per CU).  Two per SIMD (256-register budget) by default; THREE per
 // SIMD where the step loop fits the 168-register budget of three waves without scratch: the third wave fills issue slots the other
 // two leave while they wait (PIS phi^4, 131 072 x 512, d = 100: 18.9 -> 16.1 ms before the matrix-phase priority below existed, 16.1 -> 15.6
@@ -97,7 +128,8 @@ constexpr int sd_waves_of() {
 #endif
 }
 
-// PAR = 1 adds the parity-mode paths (injected noise, trajectory dump); PAR = 0 keeps them out of the step loop.
+// PAR = 1 adds the parity-mode paths (injected noise, trajectory dump); PAR = 0 keeps them out of the step loop.  PAR = 2: those paths and
+// the control-perturbation stage above (log-variance training with SDENG_FLAG_CTRL_NOISE / _DROPOUT, forward forms only).
 template <int NT, int REF, int SC, int FORM, int PAR>
 __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), (sd_waves_of<NT, REF, SC, FORM, PAR>() / 4)) k_simulate(const SimArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -569,6 +601,7 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
             rq = ref_tile(t);
             if (a.flags & SDENG_FLAG_REMOVE_REF) u[o] = u[o] - rq;
           }
+          if constexpr (PAR == 2) perturb_ctrl_tile<NT, REF != RF_GMM_FULL>(a, cf, u[o], x[t], pidx, k, t, g, d_dyn);  // everything below consumes the perturbed control
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float uv = u[o][r];
@@ -729,6 +762,9 @@ static int launch_simulate_par(const SimArgs& a, int grid, hipStream_t stream) {
 }
 template <int NT, int REF, int SC, int FORM>
 static int launch_simulate(const SimArgs& a, int grid, hipStream_t stream) {
+  if constexpr (FORM == SDENG_FORM_LIN || FORM == SDENG_FORM_EM) {  // (sdeng_simulate accepts the perturbation flags on these forms only)
+    if (a.flags & (SDENG_FLAG_CTRL_NOISE | SDENG_FLAG_CTRL_DROPOUT)) return launch_simulate_par<NT, REF, SC, FORM, 2>(a, grid, stream);
+  }
   if (a.noise_in || a.xs_out) return launch_simulate_par<NT, REF, SC, FORM, 1>(a, grid, stream);
   return launch_simulate_par<NT, REF, SC, FORM, 0>(a, grid, stream);
 }

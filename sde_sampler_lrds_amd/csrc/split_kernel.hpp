@@ -23,7 +23,7 @@
 // agree with the standard kernel to fp32 round-off, not bit for bit -- which is why the path is a flag of the ABI (sdeng.h); the Python
 // solvers set it by default for evaluation / training batches of at most 8 192 particles (solver cfg 'split_tiles').
 // Scope: ClippedCtrl, forward forms (LIN / EM), no / Gaussian / small-mixture (K <= 4) reference, d > 64, B <= 8 192, no injected noise;
-// the trajectory (xs_out) is written.  No range-safe twin of the drift net here (sim_device.hpp mlp_hidden_safe): states / activations
+// the trajectory (xs_out) is written; the control-perturbation stage of log-variance training (PERT) included.  No range-safe twin of the drift net here (sim_device.hpp mlp_hidden_safe): states / activations
 // beyond 65 504 give NaN on this path.
 #pragma once
 #include "sim_kernel.hpp"
@@ -34,7 +34,8 @@
 #define SD_SPLIT_TAB_FLOATS 256                        // per wave: its two feature tiles of one step's reference table, [K <= 4][mean, 1/var][2 tiles][16]
 __host__ __device__ inline int sd_split_lds_bytes(int NT) { return (sd_lds_weight_floats(NT) + 2 * SD_SPLIT_SLOT_FLOATS + SD_WAVES * SD_SPLIT_TAB_FLOATS) * 4; }
 
-template <int NT, int REF, int FORM>
+// PERT: the control-perturbation stage of log-variance training (sim_kernel.hpp perturb_ctrl_tile; SDENG_FLAG_CTRL_NOISE / _DROPOUT).
+template <int NT, int REF, int FORM, bool PERT>
 __global__ void __launch_bounds__(SD_THREADS, SD_WAVES / 4) k_simulate_split(const SimArgs a) {
 #ifndef SD_EXPERIMENT_WAVES  // occupancy experiments build the other kernels with another wave count; this one is then not launched
   static_assert(SD_WAVES == 8, "two tiles of four waves per workgroup");
@@ -264,6 +265,7 @@ __global__ void __launch_bounds__(SD_THREADS, SD_WAVES / 4) k_simulate_split(con
             for (int r = 0; r < 4; ++r) u[r] = __builtin_fmaf(mx[r], SD_LO_INV, u[r]);
             if (ns.inv_out != 1.0f) u = u * ns.inv_out;
             if (a.clip_model > 0.0f) clamp_tile_rare(u, a.clip_model);  // ClippedCtrl (reparam.py:42)
+            if constexpr (PERT) perturb_ctrl_tile<NT, true>(a, cf, u, x[j], pidx, k, t, g, a.d);  // the final control, at the old state
             const f32x4 z = philox_normal4(pidx, static_cast<uint32_t>(k), static_cast<uint32_t>(4 * t + g), 0u, a.seed_lo, a.seed_hi);
             f32x4 rq = zero;  // reference score of this tile (eq/sdes.py:265-279, 329-345)
             if constexpr (REF == RF_GAUSS) {
@@ -330,16 +332,21 @@ __global__ void __launch_bounds__(SD_THREADS, SD_WAVES / 4) k_simulate_split(con
   }
 }
 
-template <int NT, int REF, int FORM>
-static int launch_split(const SimArgs& a, hipStream_t stream) {
+template <int NT, int REF, int FORM, bool PERT>
+static int launch_split_k(const SimArgs& a, hipStream_t stream) {
   const size_t lds_bytes = static_cast<size_t>(sd_split_lds_bytes(NT));
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_simulate_split<NT, REF, FORM>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_simulate_split<NT, REF, FORM, PERT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      static_cast<int>(lds_bytes));
   if (e != hipSuccess) return static_cast<int>(e);
   int grid = (a.ntiles + 1) / 2;
   grid = grid > 256 ? 256 : (grid < 1 ? 1 : grid);
-  hipLaunchKernelGGL((k_simulate_split<NT, REF, FORM>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
+  hipLaunchKernelGGL((k_simulate_split<NT, REF, FORM, PERT>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
   return static_cast<int>(hipGetLastError());
+}
+template <int NT, int REF, int FORM>
+static int launch_split(const SimArgs& a, hipStream_t stream) {
+  if (a.flags & (SDENG_FLAG_CTRL_NOISE | SDENG_FLAG_CTRL_DROPOUT)) return launch_split_k<NT, REF, FORM, true>(a, stream);
+  return launch_split_k<NT, REF, FORM, false>(a, stream);
 }
 // one launcher per feature-tile count: reference kind and form are picked at run time
 template <int NT>

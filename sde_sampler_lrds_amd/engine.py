@@ -419,9 +419,18 @@ def _transition_gains(sde, s, t, ddpm):
 
 
 def coef_table(kind, ts, sde=None, *, with_ref=False, lerp=False, cancel=None, ctrl_sde=None, alpha=None, sigma=None, train=False, dim=1,
-               rescale=True) -> torch.Tensor:
+               rescale=True, ctrl_noise=None, ctrl_dropout=None) -> torch.Tensor:
     """[N,16] fp32 table (column meaning: include/sdeng.h).  ``kind``: 'ei' | 'ddpm' | 'dis_ei' | 'em' |
-    'time_reversal' | 'dds' | 'eubo_ei' | 'eubo_em'.  ``ts`` is a CPU tensor; every entry is produced by the reference's scalar formula."""
+    'time_reversal' | 'dds' | 'eubo_ei' | 'eubo_em'.  ``ts`` is a CPU tensor; every entry is produced by the reference's scalar formula.
+    ``ctrl_noise`` / ``ctrl_dropout`` (the loss's sde_ctrl_noise / sde_ctrl_dropout, forward kinds only) fill columns 12-15: sigma, p and
+    drift_coeff_t, diff_coeff_t of ``sde`` at the time the loss hands its control (generative_and_sde_ctrl, losses/oc.py:83-103)."""
+    perturb = ctrl_noise is not None or ctrl_dropout is not None
+    if perturb and kind not in ("ei", "ddpm", "dis_ei", "em", "time_reversal", "dds"):
+        raise UnsupportedByEngine(f"sde_ctrl_noise / sde_ctrl_dropout: forward loops only (table kind {kind!r})")
+    linear_sde = sde is not None and hasattr(sde, "drift_coeff_t") and hasattr(sde, "diff_coeff_t")
+    if ctrl_dropout is not None and not linear_sde:
+        raise ValueError("sde_ctrl_dropout replaces the control by -drift(t, x) / diff(t, x) of the loss's SDE (losses/oc.py:101-102), which "
+                         f"needs a linear (OU) SDE; this loss has {_name(sde) if sde is not None else 'sde=None'}")
     ts = ts.detach().to("cpu", torch.float32)
     N = ts.numel() - 1
     if kind == "cmcd_eubo":  # N+1 rows in iteration order: row k is the evaluation at time ts[N-k] (losses/oc.py:782-823)
@@ -518,6 +527,11 @@ def coef_table(kind, ts, sde=None, *, with_ref=False, lerp=False, cancel=None, c
         if with_ref:  # eq/sdes.py:228-229, 247
             s_tau = sde.s(tau)
             row[9], row[10], row[11] = s_tau, s_tau ** 2 * sde.sigma_sq(tau), s_tau ** 2
+        if perturb:  # the control's perturbation; tau is the time the loss evaluates its control at (T - s, or s for DDS / TimeReversalLoss)
+            row[12] = 0.0 if ctrl_noise is None else float(ctrl_noise)
+            row[13] = 0.0 if ctrl_dropout is None else float(ctrl_dropout)
+            if linear_sde:  # OU.drift = drift_coeff_t(t) x, OU.diff = diff_coeff_t(t) (eq/sdes.py:143-148)
+                row[14], row[15] = sde.drift_coeff_t(tau), sde.diff_coeff_t(tau)
     return out
 
 

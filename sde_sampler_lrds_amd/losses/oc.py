@@ -203,6 +203,7 @@ class BaseOCLoss:
         self._graphed = {}
         self.split_tiles = False  # True: small batches (<= _lib.SPLIT_TILES_MAX_B = 8 192, the library's own gate) ask for the low-latency kernels (SDENG_FLAG_SPLIT_TILES; fp32-round-off, not bit, equal to the standard kernel); the solvers switch it on (cfg 'split_tiles', default True)
         self.dist = None  # torch.distributed of a sharded run: eval() then returns global estimators and globally normalised weights
+        self._perturb = {}  # coefficient-table options of the control perturbation, set for the step loop of a log-variance training call
 
     # ---- reference surface -----------------------------------------------------------------
     def filter(self, rnd, samples=None):
@@ -276,9 +277,11 @@ class BaseOCLoss:
         (:269-271, :284 EM; :490-491, :499 EI / DDPM-like; :957-958, :965 DIS; :1361-1383 DDS).  KL training differentiates
         through the trajectory and is not on this path."""
         assert self.method in ("lv", "lv_traj")
-        if self.sde_ctrl_noise is not None or self.sde_ctrl_dropout is not None:
-            raise E.UnsupportedByEngine("sde_ctrl_noise / sde_ctrl_dropout perturb the simulated control (losses/oc.py:97-101): not built "
-                                        "(every conf/loss/*.yaml leaves both empty; listed under 'raises' in INTEGRATION.md)")
+        # sde_ctrl_noise / sde_ctrl_dropout (generative_and_sde_ctrl, :97-102): the step loop perturbs the control it integrates with --
+        # the perturbed control then IS the control of every term of the value (the reference writes it in place through the detached
+        # alias), while the gradient below is unchanged: c'_k z_k back through the net, along the perturbed trajectory
+        perturb = self._ctrl_perturbation()
+        coef_kw = dict(coef_kw or {}, **perturb)
         # a fresh stream per training call (the reference consumes torch's global generator): call c uses the engine's Philox
         # streams keyed by seed + c * golden-ratio increment -- for the step noise AND for an x0 left to the engine (an InitialDraw
         # materialised with the loss's fixed seed would hand every training step the same batch); call 0 is the eval stream of ``seed``
@@ -293,11 +296,13 @@ class BaseOCLoss:
         # (the kernel draws the normals of stream seed_c itself -- bit for bit the z above -- so nothing is injected and small
         # batches may take the low-latency split-tile kernel, which writes the trajectory but does not replay noise)
         seed_eval, self.seed = self.seed, seed_c
+        self._perturb = perturb
         try:
             with torch.no_grad():
                 x_n, rnd_sim, xs = simulate(x, None)
         finally:
             self.seed = seed_eval
+            self._perturb = {}
         with torch.no_grad():
             rnd_val = rnd_sim.reshape(B, 1)
             if rnd0 is not None:
@@ -306,10 +311,25 @@ class BaseOCLoss:
         # u.detach() = u (in fp32 too: (u - u/2) - u/2 = 0 exactly, which is what the reference's autograd produces).  So the only
         # part of rnd that needs a graph is the stochastic integral s_b = sum_k c'_k <u_kb, z_kb>, from one batched pass of the
         # control; it enters with value zero (s - s.detach()), and compute_loss / backward() do the rest as upstream.
-        coef = self._coef(ts, x.device, **(coef_kw or {}))  # coef[:, 0]: the net's time of step k, coef[:, 5]: c'_k
+        coef = self._coef(ts, x.device, **coef_kw)  # coef[:, 0]: the net's time of step k, coef[:, 5]: c'_k (the step loop's own table)
         zc = (z.view(N, B, d) * (coef[:, 5] if ito else torch.zeros_like(coef[:, 5])).view(N, 1, 1)).view(N * B, d)
         s = self._integral_pass(coef[:, 0].contiguous(), xs[:-1], zc)
         return self.compute_loss(rnd_val + (s - s.detach()).view(B, 1), samples=x_n)
+
+    def _ctrl_perturbation(self) -> dict:
+        """The coefficient-table options of sde_ctrl_noise / sde_ctrl_dropout ({} when both are unset), checked.  Dropout replaces the control
+        by -drift(t, x) / diff(t, x) of the loss's SDE: a loss without a linear SDE (DDS: sde=None) cannot have it -- the reference fails there
+        too, with an AttributeError."""
+        out = {}
+        if self.sde_ctrl_noise is not None:
+            out["ctrl_noise"] = float(self.sde_ctrl_noise)
+        if self.sde_ctrl_dropout is not None:
+            if not (hasattr(self.sde, "drift_coeff_t") and hasattr(self.sde, "diff_coeff_t")):
+                raise ValueError(f"{type(self).__name__}: sde_ctrl_dropout replaces the control by -drift(t, x) / diff(t, x) of the loss's SDE "
+                                 f"(losses/oc.py:101-102), which needs a linear (OU) SDE; this loss has "
+                                 f"{type(self.sde).__name__ if self.sde is not None else 'sde=None'}")
+            out["ctrl_dropout"] = float(self.sde_ctrl_dropout)
+        return out
 
     def _integral_pass(self, t_unique, xs, zc):
         """The batched control pass, eager or -- ``graph_training`` -- as a captured graph per (shape, control): at the reference's
@@ -602,6 +622,9 @@ class BaseOCLoss:
                     desc.prior = E.dist_desc(lerp_prior, device, keep)
         elif lerp_prior is not None:
             desc.prior = E.dist_desc(lerp_prior, device, keep)
+        if self._perturb:  # log-variance training with sde_ctrl_noise / sde_ctrl_dropout (BaseOCLoss._lv_loss)
+            coef_kw = dict(coef_kw or {}, **self._perturb)
+            desc.flags |= (L.FLAG_CTRL_NOISE if "ctrl_noise" in self._perturb else 0) | (L.FLAG_CTRL_DROPOUT if "ctrl_dropout" in self._perturb else 0)
         coef = self._coef(ts, device, **(coef_kw or {}))
         keep.append(coef)
         desc.coef = coef.data_ptr()
