@@ -557,8 +557,10 @@ SD_INLINE void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
   o[3] = c3;
 }
 
-// (n + 0.5) * 2^-23 with n = bits >> 9 < 2^23: every step is exact in fp32, so the single fma below is the same number
-SD_INLINE float u01(uint32_t bits) { return __builtin_fmaf(static_cast<float>(bits >> 9), 1.1920928955078125e-07f, 5.9604644775390625e-08f); }
+// (n + 0.5) * 2^-23 with n = bits >> 9 < 2^23, in two instructions: v_alignbit_b32 shifts n under the exponent of 1.0
+// ((0x7F:bits) >> 9 = 0x3F800000 | n, the float 1 + n 2^-23), and subtracting 1 - 2^-24 leaves (2n + 1) 2^-24, which fp32
+// holds exactly -- the same bits as fma(float(n), 2^-23, 2^-24) without its shift and convert (tests/test_u01_gelu_cpu.py)
+SD_INLINE float u01(uint32_t bits) { return __uint_as_float(__builtin_amdgcn_alignbit(0x7Fu, bits, 9)) - 0x1.fffffep-1f; }
 
 // normals of features 4*jb .. 4*jb+3 of global particle `pidx` at step `step`.  Counter order
 // (pidx, jb, step, stream): the first round multiplies c0 and c2 and XORs c1 into the c2 product, so the step

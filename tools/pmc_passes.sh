@@ -20,10 +20,14 @@ for SET in \
   "WRITE_SIZE GRBM_GUI_ACTIVE" ; do
   i=$((i+1))
   timeout -k 10 180 rocprofv3 --pmc $SET --output-format csv -d $OUT/p$i -- python $GRAFT_REPO_ROOT/tools/bench_kernel_only.py > $OUT/p$i.log 2>&1
-  echo "pass $i ($SET) rc=$?" >> $OUT/summary.txt
+  rc=$?
+  echo "pass $i ($SET) rc=$rc" >> $OUT/summary.txt
+  [ $rc -eq 0 ] || exit $rc  # a failed, faulted or timed-out pass ends the script: nothing more is started on that GPU
 done
 PROBE_REPS=6 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python $GRAFT_REPO_ROOT/tools/bench_kernel_only.py > $OUT/kt.log 2>&1
-echo "kernel-trace rc=$?" >> $OUT/summary.txt
+rc=$?
+echo "kernel-trace rc=$rc" >> $OUT/summary.txt
+[ $rc -eq 0 ] || exit $rc
 cp $(ls $OUT/kt/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/kernel_stats.csv 2>/dev/null
 python3 - <<PY
 import csv, glob, collections, json, sys
