@@ -128,13 +128,21 @@ extern "C" {
                                    [k,d] and aux = eigenvectors [k,d,d] (row-major, columns = vectors) of each covariance, w [k].  Forward
                                    forms without a reference drift (PIS / DDS / DIS); its log-density is not evaluated here (no
                                    FLAG_TERM_TARGET with it): SDENG_E_UNSUPPORTED otherwise. */
+#define SDENG_DIST_CHECKERBOARD 9 /* distr/checkerboard.py:6-94  2-D checkerboard: a mixture of uniform squares (d must be 2).  k squares,
+                                     loc = lower corners [k,2], scale = upper corners [k,2], w = the log-density inside each square [k]
+                                     (the caller evaluates the reference's own expression at the square's centre).  Square c holds x
+                                     when loc[c] <= x < scale[c] in both coordinates (Uniform.log_prob is half-open); the squares must be
+                                     disjoint.  log pi~(x) = w[c] inside square c, -inf outside every square and for NaN input; score = 0
+                                     (the reference returns zeros, no autograd).  Particles that end outside every square get rnd = +inf.
+                                     No sdeng_langevin_moves or sdeng_kl_adjoint with it (SDENG_E_UNSUPPORTED). */
 
 typedef struct sdeng_dist {
   int32_t kind;      /* SDENG_DIST_*                                                              */
   int32_t k;         /* GMM: number of components; LOGREG: number of data rows                    */
-  const float* loc;  /* GMM [k,d]; GAUSS_DIAG/GAUSS_FULL [d]; LOGREG: X [k,d-1]; RINGS: radii [k <= 8]  */
-  const float* scale;/* GMM [k,d]; GAUSS_DIAG [d] (std-dev); GAUSS_FULL: precision [d,d]; LOGREG: y [k] */
-  const float* w;    /* GMM, RINGS: unnormalised mixture weights [k]; GAUSS_FULL: inverse Cholesky factor L^-1 [d,d] */
+  const float* loc;  /* GMM [k,d]; GAUSS_DIAG/GAUSS_FULL [d]; LOGREG: X [k,d-1]; RINGS: radii [k <= 8]; CHECKERBOARD: low [k,2] */
+  const float* scale;/* GMM [k,d]; GAUSS_DIAG [d] (std-dev); GAUSS_FULL: precision [d,d]; LOGREG: y [k]; CHECKERBOARD: high [k,2] */
+  const float* w;    /* GMM, RINGS: unnormalised mixture weights [k]; GAUSS_FULL: inverse Cholesky factor L^-1 [d,d];
+                        CHECKERBOARD: log-density inside each square [k] */
   float p0, p1, p2, p3; /* ISO_GAUSS: loc, scale, norm_const = -0.5*d*log(2*pi*scale^2), scale^2 (both as the
                            reference computes them in fp32, distr/gauss.py:759-760); PHI4: a, b, beta;
                            LOGREG: weight_scale, intercept_mean, intercept_scale, threshold;

@@ -1,5 +1,5 @@
 // CMCD step loop (ControlledLangevinSDELoss.simulate, losses/oc.py:666-755) for a Bayesian logistic-regression
-// target (distr/logistic_regression.py) or a diagonal Gaussian mixture target, with a full-covariance, diagonal or
+// target (distr/logistic_regression.py), a diagonal Gaussian mixture, phi^4, rings or checkerboard target, with a full-covariance, diagonal or
 // isotropic Gaussian prior, on gfx950.
 //
 // The reference evaluates, per step, the drift net twice and the annealed score twice, each target score being
@@ -21,7 +21,9 @@ struct CmcdArgs {
 __host__ __device__ inline int cmcd_lds_floats(int NT, int n_rows) { return sd_lds_weight_floats(NT) + sd_lr_floats(NT, n_rows); }
 
 // (u, b) at (time index ki, state x): u = ctrl(t, x) (reparam.py:112-117), b = annealed drift (eq/sdes.py:101-110)
-enum { CT_LOGREG = 0, CT_GMM = 1, CT_PHI4 = 2 };  // target kind is a template parameter: one score body per kernel
+// (CT_RINGS, CT_ZERO: the 2-D toy targets, d <= 16 kernels only.  CT_ZERO is a target whose score is identically zero -- the
+// checkerboard, distr/checkerboard.py:81-83 -- so the annealed drift is the prior's score alone.)
+enum { CT_LOGREG = 0, CT_GMM = 1, CT_PHI4 = 2, CT_RINGS = 3, CT_ZERO = 4 };  // target kind is a template parameter: one score body per kernel
 
 // TWO = true also returns b2, the drift with a second pair of annealing weights (the noising loop of compute_eubo
 // needs drift(t, y) for the cost and drift(s, y) for the next move: same scores, two mixes)
@@ -53,6 +55,12 @@ SD_INLINE void cmcd_eval(const CmcdArgs& a, const f32x4 (&x)[NT], int ki, float 
   } else if constexpr (TGT == CT_GMM) {
     // diagonal Gaussian / mixture target (distr/gauss.py:97-107, 124-126): tables prepared by k_dist_tables
     gmm_score<NT>(x, s.target.tab, s.target.consts, 4, s.target.k, s.target.p0, g, ts);
+  } else if constexpr (TGT == CT_RINGS) {
+    static_assert(NT == 1, "rings: d = 2");
+    ts[0] = rings_score(x[0], s.target, g);  // distr/rings.py:100-109 (0 on the pad features)
+  } else if constexpr (TGT == CT_ZERO) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) ts[t] = zero;
   } else {
     static_assert(TGT != CT_LOGREG || NT <= 4, "logistic regression: d <= 64 (design matrix in LDS)");
     // (two copies of the body on purpose: a pointer selected between LDS and global memory would make every A-operand read a flat load)
@@ -334,6 +342,13 @@ static int launch_cmcd_t(const CmcdArgs& a, int grid, hipStream_t stream) {
 }
 template <int NT>
 static int launch_cmcd(const CmcdArgs& a, int grid, hipStream_t stream) {
+  if constexpr (NT == 1) {  // the 2-D toy targets (the host checks d = 2): both directions
+    const bool eubo = a.s.form == SDENG_FORM_CMCD_EUBO;
+    if (a.s.target.kind == SDENG_DIST_RINGS)
+      return eubo ? launch_cmcd_t<1, CT_RINGS, true>(a, grid, stream) : launch_cmcd_t<1, CT_RINGS, false>(a, grid, stream);
+    if (a.s.target.kind == SDENG_DIST_CHECKERBOARD)
+      return eubo ? launch_cmcd_t<1, CT_ZERO, true>(a, grid, stream) : launch_cmcd_t<1, CT_ZERO, false>(a, grid, stream);
+  }
   if (a.s.form == SDENG_FORM_CMCD_EUBO) {  // noising loop: mixture / Gaussian targets (the targets that can be sampled from)
     if (a.s.target.kind == SDENG_DIST_GMM_DIAG || a.s.target.kind == SDENG_DIST_GAUSS_DIAG) return launch_cmcd_t<NT, CT_GMM, true>(a, grid, stream);
     return static_cast<int>(hipErrorInvalidValue);

@@ -529,6 +529,17 @@ __device__ float dist_logp_row(const DistEvalArgs& a, const float* x) {
       m_run = m_new;
     }
     out = ((m_run + logf(l_run)) - 1.8378770664093453f) - logf(r);
+  } else if (ds.kind == SDENG_DIST_CHECKERBOARD) {
+    // distr/checkerboard.py:77-79: MixtureSameFamily(Categorical, Independent(Uniform(low, high))).log_prob.  Uniform.log_prob is
+    // log((low <= x) * (high > x)) - log(high - low): the disjoint squares leave at most one finite component, which logsumexp returns
+    // unchanged -- its constant, aux0 = low [k,2], aux1 = high [k,2], tab = constants [k].  -inf outside every square and for NaN.
+    out = -INFINITY;
+    for (int k = 0; k < ds.k; ++k) {
+      const float* lo = ds.aux0 + 2 * k;
+      const float* hi = ds.aux1 + 2 * k;
+      const bool in = (lo[0] <= x[0]) & (hi[0] > x[0]) & (lo[1] <= x[1]) & (hi[1] > x[1]);
+      out = in ? ds.tab[k] : out;
+    }
   }
   if (ds.clip > 0.0f) out = clampf(out, ds.clip);
   return out;
@@ -607,6 +618,9 @@ __device__ void dist_score_row(const DistEvalArgs& a, const float* x, float* sc)
     const f32x4 r = rings_score(f32x4{x[0], x[1], 0.0f, 0.0f}, ds, 0);
     sc[0] = r[0];
     sc[1] = r[1];
+  } else if (ds.kind == SDENG_DIST_CHECKERBOARD) {  // distr/checkerboard.py:81-83: zeros
+    sc[0] = 0.0f;
+    sc[1] = 0.0f;
   }
 }
 
@@ -937,7 +951,9 @@ __global__ void k_logz_final(const float* partials, const float* partials2, int 
   }
   const float fB = static_cast<float>(B);
   stats[0] = s1 / fB;
-  stats[1] = (mx + logf(se)) - logf(fB);
+  // torch.logsumexp zeroes an infinite maximum before it shifts: every -rnd = -inf (all particles outside a target's support) gives
+  // -inf, not exp(-inf - -inf) = NaN; a finite maximum takes the same instructions as before
+  stats[1] = (__builtin_isinf(mx) ? mx : (mx + logf(se))) - logf(fB);
   stats[2] = B > 1 ? sv / (fB - 1.0f) : 0.0f;
   stats[3] = (se * se) / se2 / fB;
   stats[4] = mx;

@@ -271,6 +271,11 @@ static int build_dist(const sdeng_dist& in, int d, int dpad, float* ws, DistDev&
       if (!in.loc || !in.w || in.k < 1 || in.k > 8 || !(in.p0 > 0.0f)) return fail(SDENG_E_INVALID, "RINGS needs radii, weights, 1 <= k <= 8, scale > 0");
       out.aux0 = in.loc; out.aux1 = in.w;
       return 0;
+    case SDENG_DIST_CHECKERBOARD:
+      if (d != 2) return fail(SDENG_E_INVALID, "CHECKERBOARD is two-dimensional (d = %d)", d);
+      if (!in.loc || !in.scale || !in.w || in.k < 1) return fail(SDENG_E_INVALID, "CHECKERBOARD needs the low / high corner tables, the per-square constants and k >= 1");
+      out.aux0 = in.loc; out.aux1 = in.scale; out.tab = in.w;
+      return 0;
     default:
       return fail(SDENG_E_UNSUPPORTED, "unknown distribution kind %d", in.kind);
   }
@@ -371,12 +376,13 @@ static int prepare_logreg(const sdeng_desc* d, const Layout& L, float* ws, int D
   return 0;
 }
 
-// ControlledLangevinSDELoss.simulate (losses/oc.py:666-755): logistic-regression target, Gaussian prior
+// ControlledLangevinSDELoss.simulate (losses/oc.py:666-755): logistic-regression, mixture, phi^4, rings or checkerboard target, Gaussian prior
 static int simulate_cmcd(const sdeng_desc* d, const Layout& L, float* ws, int DT, SimArgs& a, hipStream_t s) {
   const int dpad = 16 * DT;
   const bool logreg = d->target.kind == SDENG_DIST_LOGREG;
-  if (!logreg && d->target.kind != SDENG_DIST_GMM_DIAG && d->target.kind != SDENG_DIST_GAUSS_DIAG && d->target.kind != SDENG_DIST_PHI4)
-    return fail(SDENG_E_UNSUPPORTED, "CMCD kernel: target must be LOGREG, GMM_DIAG, GAUSS_DIAG or PHI4 (kind %d)", d->target.kind);
+  const bool toy = d->target.kind == SDENG_DIST_RINGS || d->target.kind == SDENG_DIST_CHECKERBOARD;  // 2-D: build_dist checks d = 2
+  if (!logreg && !toy && d->target.kind != SDENG_DIST_GMM_DIAG && d->target.kind != SDENG_DIST_GAUSS_DIAG && d->target.kind != SDENG_DIST_PHI4)
+    return fail(SDENG_E_UNSUPPORTED, "CMCD kernel: target must be LOGREG, GMM_DIAG, GAUSS_DIAG, PHI4, RINGS or CHECKERBOARD (kind %d)", d->target.kind);
   if (logreg && DT > 4) return fail(SDENG_E_UNSUPPORTED, "CMCD kernel: logistic regression with d <= 64 (got %d)", d->d);
   const int n = logreg ? d->target.k : 0;  // data rows held in LDS
   if (logreg && n < 1) return fail(SDENG_E_INVALID, "CMCD kernel: logistic regression without data rows");
@@ -411,8 +417,8 @@ static int simulate_cmcd(const sdeng_desc* d, const Layout& L, float* ws, int DT
   TerminalArgs t;
   t.B = d->B; t.d = d->d; t.dpad = dpad;
   if (eubo) {  // rnd0 = -log pi~(x_in)   (losses/oc.py:779)
-    if (d->target.kind != SDENG_DIST_GMM_DIAG && d->target.kind != SDENG_DIST_GAUSS_DIAG)
-      return fail(SDENG_E_UNSUPPORTED, "CMCD compute_eubo kernels: diagonal Gaussian / mixture targets (kind %d)", d->target.kind);
+    if (d->target.kind != SDENG_DIST_GMM_DIAG && d->target.kind != SDENG_DIST_GAUSS_DIAG && !toy)
+      return fail(SDENG_E_UNSUPPORTED, "CMCD compute_eubo kernels: diagonal Gaussian / mixture, rings or checkerboard targets (kind %d)", d->target.kind);
     SD_HIP(hipMemsetAsync(ws + L.rnd_init, 0, sizeof(float) * d->B, s));
     t.ref = target; t.target = target; t.use_ref = 0; t.use_target = 1; t.x = d->x_in; t.rnd = ws + L.rnd_init;
     SD_HIP(sd_launch_terminal(t, s));
@@ -842,6 +848,8 @@ static int check_adjoint(const sdeng_desc* d, bool ext_score) {
                                      "target kind %d)", d->net.ctrl_kind, d->target.kind);
   if (d->net.ctrl_kind == SDENG_CTRL_LERP && d->prior.kind != SDENG_DIST_ISO_GAUSS)
     return fail(SDENG_E_UNSUPPORTED, "LerpCtrl needs an IsotropicGauss prior (kind %d given)", d->prior.kind);
+  if (d->target.kind == SDENG_DIST_CHECKERBOARD || d->prior.kind == SDENG_DIST_CHECKERBOARD)
+    return fail(SDENG_E_UNSUPPORTED, "kl_adjoint: no adjoint for a checkerboard target (KL training takes the per-step path)");
   if (d->ref.kind != SDENG_REF_NONE && d->ref.kind != SDENG_REF_GAUSS_DIAG && d->ref.kind != SDENG_REF_GMM_DIAG)
     return fail(SDENG_E_UNSUPPORTED, "kl_adjoint: no reference, or a diagonal Gaussian / mixture reference (ref.kind %d)", d->ref.kind);
   if (d->ref.kind != SDENG_REF_NONE && ((d->ref.kind == SDENG_REF_GMM_DIAG && d->ref.k < 1) || !d->ref.means_init || !d->ref.vars_init))
@@ -962,6 +970,8 @@ extern "C" int sdeng_langevin_moves(const sdeng_dist* prior, const sdeng_dist* t
   if (!target || !x || !lp || !grad || !step || B < 0 || d < 1 || n_moves < 0 || keep_from < 0) return fail(SDENG_E_INVALID, "bad argument");
   if (d > 255) return fail(SDENG_E_UNSUPPORTED, "langevin_moves: d <= 255 (chain rows live in LDS), got %d", d);
   if ((z == nullptr) != (u == nullptr) && !unadjusted) return fail(SDENG_E_INVALID, "MALA: inject both the normals and the uniforms, or neither");
+  if (target->kind == SDENG_DIST_CHECKERBOARD || (prior && prior->kind == SDENG_DIST_CHECKERBOARD))
+    return fail(SDENG_E_UNSUPPORTED, "langevin_moves: no moves on a checkerboard (its log-density is -inf on a set of positive mass)");
   if (B == 0 || n_moves == 0) return 0;
   const int dpad = 16 * ((d + 15) / 16);
   const size_t need = sdeng_langevin_moves_workspace_bytes(prior, target, d);

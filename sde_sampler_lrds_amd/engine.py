@@ -114,6 +114,15 @@ def dist_desc(obj, device, keep, clip=None, score_only=False) -> L.Dist:
         ds.w = _dev_f32(obj.radius_dist.mixture_distribution.probs, device, keep)
         ds.p0 = float(obj.radius_dist.component_distribution.scale.reshape(-1)[0])
         return ds
+    if n == "Checkerboard":  # distr/checkerboard.py: uniform squares; this package's mirror and the reference's object alike
+        comp = obj.distr.component_distribution.base_dist
+        ds.kind = L.DIST_CHECKERBOARD
+        ds.k = int(comp.low.shape[0])
+        ds.loc = _dev_f32(comp.low, device, keep)
+        ds.scale = _dev_f32(comp.high, device, keep)
+        with torch.no_grad():  # each square's log-density: the object's own expression at the square's centre (it is constant inside)
+            ds.w = _dev_f32(obj.unnorm_log_prob((comp.low + comp.high) / 2.0).reshape(-1), device, keep)
+        return ds
     if n in ("GMMFull", "TwoModesFull") and score_only:
         # score_mog_full inside the step loop (distr/gauss.py:110-121): the kernel takes each covariance in its eigen form, decomposed
         # once per parameter version in fp64 (the reference inverts the covariances once, in fp32, at construction)
@@ -716,6 +725,8 @@ def langevin_moves(target, prior, x, lp, grad, step, n_moves, *, t=None, keep_fr
     for name, v in (("x", x), ("lp", lp), ("grad", grad), ("step", step)):
         if v.dtype != torch.float32 or not v.is_contiguous() or not v.is_cuda:
             raise ValueError(f"langevin_moves: {name} must be a contiguous float32 CUDA tensor (it is updated in place)")
+    if _name(target) == "Checkerboard" or _name(prior) == "Checkerboard":
+        raise UnsupportedByEngine("langevin_moves: no moves on a checkerboard (log-density -inf on a set of positive mass; zero score)")
     dt = dist_desc(target, device, keep)
     dp = dist_desc(prior, device, keep) if prior is not None else None
     z = u = None

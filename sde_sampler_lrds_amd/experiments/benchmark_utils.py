@@ -9,6 +9,7 @@ from functools import partial
 
 import torch
 
+from ..distr.checkerboard import Checkerboard
 from ..distr.gauss import BracketTwoModes, ManyModes, TwoModes, TwoModesFull
 from ..distr.logistic_regression import LogisticRegression
 from ..distr.phi_four import PhiFour
@@ -58,6 +59,8 @@ def make_target_details(target_name, **kwargs):
         return dict(name="phi_four", dim=kwargs.get("dim", 100), b=kwargs.get("b", 0.0))
     if target_name == "rings":
         return dict(name="rings")
+    if target_name == "checkerboard":
+        return dict(name="checkerboard")
     if target_name in LOGREG_TARGETS:  # benchmark_utils.py:84-91
         return dict(name=target_name)
     raise UnsupportedByEngine(f"Target {target_name} has no HIP log-density / score kernel.")
@@ -78,6 +81,8 @@ def _make_target(details):
         return PhiFour(**{"dim": 100, "a": 0.1, "b": 0.0, "dim_phys": 1, "beta": 20.0, **d})
     if name == "rings":  # conf/target/rings.yaml
         return Rings(**{"dim": 2, "n_reference_samples": 10000, **d})
+    if name == "checkerboard":  # conf/target/checkerboard.yaml
+        return Checkerboard(**{"dim": 2, "width": 4, "unequilibrated": True, **d})
     if name in LOGREG_TARGETS:  # the design matrix: register_dataset / $SDENG_DATA_DIR/<name>.pt (distr/logistic_regression.py)
         return LogisticRegression(**{**LOGREG_TARGETS[name], **d})
     if "object" in details:

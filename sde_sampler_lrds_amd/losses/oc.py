@@ -787,7 +787,7 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
 
     def compute_eubo(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, use_ema=False, *, noise=None):
         """losses/oc.py:757-828: the CMCD loop run from target samples with the control subtracted, one HIP launch
-        (SDENG_FORM_CMCD_EUBO; diagonal Gaussian / mixture targets -- the ones that can be sampled).  ``x`` is NOT modified
+        (SDENG_FORM_CMCD_EUBO; diagonal Gaussian / mixture, rings and checkerboard targets -- the ones that can be sampled).  ``x`` is NOT modified
         (upstream rebinds it, :820)."""
         _, rnd, _ = self.simulate(ts, x, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False, use_ema=use_ema,
                                   noise=noise, eubo=True)
