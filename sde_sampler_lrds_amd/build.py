@@ -37,55 +37,81 @@ if os.environ.get("SDENG_CXXFLAGS"):  # experiment knob: extra compiler flags (e
 if os.environ.get("SDENG_WAVES"):  # experiment knob: waves per workgroup (8 = 2 per SIMD, 4 = 1 per SIMD)
     FLAGS.append("-DSD_WAVES=" + os.environ["SDENG_WAVES"])
 
-DTS, REFS, SCS, FORMS = (1, 2, 3, 4, 5, 6, 7, 8), (0, 1, 2, 3), (0, 1, 2), (0, 1)  # DTS: feature tiles of 16, NT = ceil(d / 16)
-DTS_FULL = (1, 2, 3, 4, 6, 8)  # full-covariance reference: two staged pieces of NT/2 output tiles when NT > 4
+DTS = (1, 2, 3, 4, 5, 6, 7, 8)  # feature tiles of 16, NT = ceil(d / 16)
+DTS_FULL = (1, 2, 3, 4, 6, 8)    # full-covariance reference: two staged pieces of NT/2 output tiles when NT > 4 (5 and 7 run on 6 and 8)
+LIN, EM, EUBO = 0, 1, 3          # SDENG_FORM_*
+
+
+def _sim(nt, ref, sc, forms):
+    """k_simulate instances: PAR 0 (plain), 1 (injected noise / trajectory), and 2 (control perturbation) on the forward forms."""
+    return [("sim", nt, (ref, sc, fm, par)) for fm in forms for par in ((0, 1, 2) if fm in (LIN, EM) else (0, 1))]
+
+
+def _cmcd(nt):
+    """k_simulate_cmcd instances: TGT (CT_LOGREG 0, CT_GMM 1, CT_PHI4 2, CT_RINGS 3, CT_ZERO 4) x EUBO x PAR."""
+    tgts = [(1, 0), (1, 1), (2, 0)] + ([(0, 0)] if nt <= 4 else []) + ([(3, 0), (3, 1), (4, 0), (4, 1)] if nt == 1 else [])
+    return [("cmcd", nt, (tgt, eubo, par)) for tgt, eubo in tgts for par in (0, 1)]
+
+
+# Every kernel instance, grouped by translation unit (csrc/gen/<unit>.hip): unit -> [(family, NT, template parameters after NT)].
+# The units and gen/registry.hip -- the sorted table sdeng_api.hip looks launchers up in -- are both generated from this one list.
+# REF: 0 none, 1 Gauss, 2 mixture (K <= 4), 3 larger mixture, 4 full covariance, 5 shared variance on the matrix pipe.
+# SC (in-loop score of a Score / Lerp / CancelDrift control): 0 none, 1 mixture / rings, 2 phi^4, 3 logistic regression, 4 the
+# full-covariance target held in the reference slot.
+UNITS = {
+    **{f"sim_{nt}_{ref}_{sc}": _sim(nt, ref, sc, (LIN, EM) + ((EUBO,) if (sc == 0) != (ref == 0) else ()))
+       for nt in DTS for ref in (0, 1, 2, 3) for sc in (0, 1, 2)},
+    **{f"sim_{nt}_0_3": _sim(nt, 0, 3, (LIN, EM)) for nt in (1, 2, 3, 4)},  # logistic-regression design matrix in LDS: d <= 64
+    **{f"sim_{nt}_4_0": _sim(nt, 4, 0, (LIN, EM, EUBO)) for nt in DTS_FULL},
+    **{f"sim_{nt}_4_4": _sim(nt, 4, 4, (LIN, EM)) for nt in DTS_FULL},
+    **{f"sim_{nt}_5_0": _sim(nt, 5, 0, (LIN, EM)) for nt in DTS},
+    **{f"ctrl_{nt}": [("ctrl", nt, (sc,)) for sc in (0, 1, 2)] for nt in DTS},
+    # low-latency small-batch kernels: a tile's features over four waves, d > 64; REF 0..2 x form x PERT
+    **{f"split_{nt}": [("split", nt, (ref, fm, pert)) for ref in (0, 1, 2) for fm in (LIN, EM) for pert in (0, 1)] for nt in (5, 6, 7, 8)},
+    **{f"cmcd_{nt}": _cmcd(nt) for nt in DTS},
+    # drift-net VJP (GX: with the input gradient) and the KL adjoint (SCORE: ADJ_NONE, _GMM, _PHI4, _EXT) share a unit
+    **{f"vjp_{nt}": [("vjp", nt, (gx,)) for gx in (1, 0)] + [("adj", nt, (sc,)) for sc in (0, 1, 2, 3)] for nt in DTS},
+    "euler_inst": [("euler", nt, (sc,)) for nt in DTS for sc in (0, 1, 2)],  # SDEs without a drift net
+}
+# family -> (header, launcher template, registry enum); the enum order is the registry's sort order (sim_common.hpp)
+FAMILIES = {
+    "sim": ("sim_kernel.hpp", "launch_simulate", "SD_FAM_SIM"),
+    "ctrl": ("sim_kernel.hpp", "launch_ctrl_forward", "SD_FAM_CTRL"),
+    "split": ("split_kernel.hpp", "launch_split", "SD_FAM_SPLIT"),
+    "euler": ("euler_kernel.hpp", "launch_euler", "SD_FAM_EULER"),
+    "cmcd": ("cmcd_kernel.hpp", "launch_cmcd", "SD_FAM_CMCD"),
+    "vjp": ("grad_kernel.hpp", "launch_ctrl_vjp", "SD_FAM_VJP"),
+    "adj": ("grad_kernel.hpp", "launch_kl_adjoint", "SD_FAM_ADJ"),
+}
+
+
+def _launcher(fam, nt, params):
+    return f"sd_launch_{fam}_{nt}_" + "_".join(map(str, params))
 
 
 def sources():
     os.makedirs(GEN, exist_ok=True)
-    srcs = [os.path.join(CSRC, "sdeng_api.hip"), os.path.join(CSRC, "prep_kernels.hip"), os.path.join(CSRC, "cmcd_inst.hip"),
-            os.path.join(CSRC, "euler_inst.hip")]
-    for dt in DTS:  # fused forward + backward of the drift net (grad_kernel.hpp): the training direction's batched control pass
-        path = os.path.join(GEN, f"vjp_{dt}.hip")
-        _write_if_changed(path, '#include "../grad_kernel.hpp"\n' + f"SD_DEFINE_VJP({dt})\n")
-        srcs.append(path)
-    for dt in DTS:  # CMCD kernels (3 target kinds each)
-        path = os.path.join(GEN, f"cmcd_{dt}.hip")
-        _write_if_changed(path, '#include "../cmcd_kernel.hpp"\n'
-                                f"int sd_launch_cmcd_{dt}(const CmcdArgs& a, int grid, hipStream_t s) {{ return launch_cmcd<{dt}>(a, grid, s); }}\n")
-        srcs.append(path)
-    for dt in (1, 2, 3, 4):  # in-loop logistic-regression score (SC = 3): no reference, d <= 64, forward forms only
-        path = os.path.join(GEN, f"sim_{dt}_0_3.hip")
-        _write_if_changed(path, '#include "../sim_kernel.hpp"\n' + "".join(f"SD_DEFINE_SIM({dt}, 0, 3, {fm})\n" for fm in FORMS))
-        srcs.append(path)
-    for dt in DTS_FULL:  # full-covariance mixture reference (REF = 4): ClippedCtrl; forward forms and the noising loop (3 = EUBO)
-        path = os.path.join(GEN, f"sim_{dt}_4_0.hip")
-        _write_if_changed(path, '#include "../sim_kernel.hpp"\n' + "".join(f"SD_DEFINE_SIM({dt}, 4, 0, {fm})\n" for fm in FORMS + (3,)))
-        srcs.append(path)
-    for dt in DTS_FULL:  # full-covariance mixture TARGET of a score control, held in the reference slot (REF = 4, SC = 4): forward forms
-        path = os.path.join(GEN, f"sim_{dt}_4_4.hip")
-        _write_if_changed(path, '#include "../sim_kernel.hpp"\n' + "".join(f"SD_DEFINE_SIM({dt}, 4, 4, {fm})\n" for fm in FORMS))
-        srcs.append(path)
-    for dt in (5, 6, 7, 8):  # low-latency small-batch kernels (split_kernel.hpp): a tile's features over four waves, d > 64
-        path = os.path.join(GEN, f"split_{dt}.hip")
-        _write_if_changed(path, '#include "../split_kernel.hpp"\n' + f"SD_DEFINE_SPLIT({dt})\n")
-        srcs.append(path)
-    for dt in DTS:  # shared-variance mixture reference on the matrix pipe (REF = 5): ClippedCtrl, forward forms
-        path = os.path.join(GEN, f"sim_{dt}_5_0.hip")
-        _write_if_changed(path, '#include "../sim_kernel.hpp"\n' + "".join(f"SD_DEFINE_SIM({dt}, 5, 0, {fm})\n" for fm in FORMS))
-        srcs.append(path)
-    for dt in DTS:
-        for rf in REFS:
-            for sc in SCS:
-                path = os.path.join(GEN, f"sim_{dt}_{rf}_{sc}.hip")
-                # 3 = SDENG_FORM_EUBO: reference-SDE losses with a ClippedCtrl, or DIS (score control, no reference)
-                forms = FORMS + ((3,) if ((sc == 0) != (rf == 0)) else ())
-                body = '#include "../sim_kernel.hpp"\n' + "".join(f"SD_DEFINE_SIM({dt}, {rf}, {sc}, {fm})\n" for fm in forms)
-                _write_if_changed(path, body)
-                srcs.append(path)
-        path = os.path.join(GEN, f"ctrl_{dt}.hip")
-        _write_if_changed(path, '#include "../sim_kernel.hpp"\n' + "".join(f"SD_DEFINE_CTRL({dt}, {sc})\n" for sc in SCS))
-        srcs.append(path)
+    srcs = [os.path.join(CSRC, n) for n in ("sdeng_api.hip", "prep_kernels.hip", "cmcd_inst.hip")]
+    for unit, insts in UNITS.items():
+        headers = sorted({FAMILIES[fam][0] for fam, _, _ in insts})
+        body = "".join(f'#include "../{h}"\n' for h in headers) + "".join(
+            f"int {_launcher(fam, nt, p)}(const void* a, hipStream_t s) {{ return {FAMILIES[fam][1]}<{nt}, {', '.join(map(str, p))}>(a, s); }}\n"
+            for fam, nt, p in insts)
+        srcs.append(os.path.join(GEN, unit + ".hip"))
+        _write_if_changed(srcs[-1], body)
+    order = list(FAMILIES)
+    insts = sorted(((order.index(fam), nt, p, fam) for v in UNITS.values() for fam, nt, p in v))
+    body = ('// generated by build.py from UNITS: every kernel instance and its launcher, sorted by key (host code only)\n'
+            '#include "../sim_common.hpp"\n#ifndef __HIP_DEVICE_COMPILE__\n' +
+            "".join(f"int {_launcher(fam, nt, p)}(const void* a, hipStream_t s);\n" for _, nt, p, fam in insts) +
+            "constexpr SdKernelEntry sd_registry[] = {\n" +
+            "".join(f"    {{sd_key({FAMILIES[fam][2]}, {nt}, {', '.join(map(str, p))}), {_launcher(fam, nt, p)}}},\n" for _, nt, p, fam in insts) +
+            "};\nconst int sd_registry_size = sizeof(sd_registry) / sizeof(sd_registry[0]);\n"
+            "constexpr bool sd_registry_sorted() {\n  for (int i = 1; i < sizeof(sd_registry) / sizeof(sd_registry[0]); ++i)\n"
+            "    if (!(sd_registry[i - 1].key < sd_registry[i].key)) return false;\n  return true;\n}\n"
+            'static_assert(sd_registry_sorted(), "registry keys must be unique and sorted (build.py FAMILIES order = SD_FAM_* order)");\n#endif\n')
+    srcs.append(os.path.join(GEN, "registry.hip"))
+    _write_if_changed(srcs[-1], body)
     return srcs
 
 

@@ -326,35 +326,10 @@ __global__ void __launch_bounds__(SD_THREADS, SD_WAVES / 4) k_simulate_cmcd(cons
   }
 }
 
-template <int NT, int TGT, bool EUBO, int PAR>
-static int launch_cmcd_p(const CmcdArgs& a, int grid, hipStream_t stream) {
+// host-side launcher of one instance (gen/cmcd_<NT>.hip); sdeng_api.hip select_cmcd picks TGT, EUBO and PAR
+template <int NT, int TGT, int EUBO, int PAR>
+static int launch_cmcd(const void* p, hipStream_t stream) {
+  const CmcdArgs& a = *static_cast<const CmcdArgs*>(p);
   const size_t lds_bytes = static_cast<size_t>(a.s.lr.in_lds ? cmcd_lds_floats(NT, a.s.lr.n_rows) : sd_lds_weight_floats(NT)) * sizeof(float);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_simulate_cmcd<NT, TGT, EUBO, PAR>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds_bytes));
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL((k_simulate_cmcd<NT, TGT, EUBO, PAR>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
-  return static_cast<int>(hipGetLastError());
-}
-template <int NT, int TGT, bool EUBO>
-static int launch_cmcd_t(const CmcdArgs& a, int grid, hipStream_t stream) {
-  if (a.s.noise_in || a.s.xs_out) return launch_cmcd_p<NT, TGT, EUBO, 1>(a, grid, stream);
-  return launch_cmcd_p<NT, TGT, EUBO, 0>(a, grid, stream);
-}
-template <int NT>
-static int launch_cmcd(const CmcdArgs& a, int grid, hipStream_t stream) {
-  if constexpr (NT == 1) {  // the 2-D toy targets (the host checks d = 2): both directions
-    const bool eubo = a.s.form == SDENG_FORM_CMCD_EUBO;
-    if (a.s.target.kind == SDENG_DIST_RINGS)
-      return eubo ? launch_cmcd_t<1, CT_RINGS, true>(a, grid, stream) : launch_cmcd_t<1, CT_RINGS, false>(a, grid, stream);
-    if (a.s.target.kind == SDENG_DIST_CHECKERBOARD)
-      return eubo ? launch_cmcd_t<1, CT_ZERO, true>(a, grid, stream) : launch_cmcd_t<1, CT_ZERO, false>(a, grid, stream);
-  }
-  if (a.s.form == SDENG_FORM_CMCD_EUBO) {  // noising loop: mixture / Gaussian targets (the targets that can be sampled from)
-    if (a.s.target.kind == SDENG_DIST_GMM_DIAG || a.s.target.kind == SDENG_DIST_GAUSS_DIAG) return launch_cmcd_t<NT, CT_GMM, true>(a, grid, stream);
-    return static_cast<int>(hipErrorInvalidValue);
-  }
-  if (a.s.target.kind == SDENG_DIST_PHI4) return launch_cmcd_t<NT, CT_PHI4, false>(a, grid, stream);
-  if (a.s.target.kind != SDENG_DIST_LOGREG) return launch_cmcd_t<NT, CT_GMM, false>(a, grid, stream);
-  if constexpr (NT <= 4) return launch_cmcd_t<NT, CT_LOGREG, false>(a, grid, stream);
-  return static_cast<int>(hipErrorInvalidValue);
+  return sd_launch_kernel(k_simulate_cmcd<NT, TGT, EUBO != 0, PAR>, sd_grid(a.s.ntiles), SD_THREADS, lds_bytes, stream, a);
 }

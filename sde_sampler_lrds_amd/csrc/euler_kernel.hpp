@@ -67,8 +67,10 @@ __global__ void __launch_bounds__(SD_EULER_THREADS) k_euler(const SimArgs a) {
   }
 }
 
+// host-side launcher of one instance (gen/euler_inst.hip); no dynamic LDS
 template <int NT, int SC>
-static int launch_euler_one(const SimArgs& a, hipStream_t stream) {
+static int launch_euler(const void* p, hipStream_t stream) {
+  const SimArgs& a = *static_cast<const SimArgs*>(p);
   const int waves = SD_EULER_THREADS / 64;
   int grid = (a.ntiles + waves - 1) / waves;
   if (grid > 256 * 8) grid = 256 * 8;  // 8 resident workgroups per CU cover the chip; beyond that tiles are strided
@@ -76,12 +78,3 @@ static int launch_euler_one(const SimArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL((k_euler<NT, SC>), dim3(grid), dim3(SD_EULER_THREADS), 0, stream, a);
   return static_cast<int>(hipGetLastError());
 }
-template <int NT>
-static int launch_euler(const SimArgs& a, int sc, hipStream_t stream) {
-  if (sc == SC_NONE) return launch_euler_one<NT, SC_NONE>(a, stream);
-  if (sc == SC_GMM) return launch_euler_one<NT, SC_GMM>(a, stream);
-  if (sc == SC_PHI4) return launch_euler_one<NT, SC_PHI4>(a, stream);
-  return static_cast<int>(hipErrorInvalidValue);
-}
-#define SD_DEFINE_EULER(NT) \
-  int sd_launch_euler_##NT(const SimArgs& a, int sc, hipStream_t s) { return launch_euler<NT>(a, sc, s); }

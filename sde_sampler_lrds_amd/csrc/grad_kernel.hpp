@@ -485,36 +485,14 @@ __global__ void __launch_bounds__(SD_THREADS, SD_WAVES / 4) k_kl_adjoint(const A
   }
 }
 
-template <int NT>
-static int launch_ctrl_vjp(const VjpArgs& a, int grid, hipStream_t stream) {
-  const size_t lds_bytes = static_cast<size_t>(2 * sd_off_wout(NT)) * sizeof(float);
-  hipError_t e;
-  if (a.gx) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctrl_vjp<NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-    if (e != hipSuccess) return static_cast<int>(e);
-    hipLaunchKernelGGL((k_ctrl_vjp<NT, true>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
-  } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctrl_vjp<NT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-    if (e != hipSuccess) return static_cast<int>(e);
-    hipLaunchKernelGGL((k_ctrl_vjp<NT, false>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
-  }
-  return static_cast<int>(hipGetLastError());
+// host-side launchers, one per instance (gen/vjp_<NT>.hip); sdeng_api.hip picks GX (gx requested) and SCORE (has_score)
+template <int NT, int GX>
+static int launch_ctrl_vjp(const void* p, hipStream_t stream) {
+  const VjpArgs& a = *static_cast<const VjpArgs*>(p);
+  return sd_launch_kernel(k_ctrl_vjp<NT, GX != 0>, sd_grid(a.ntiles), SD_THREADS, static_cast<size_t>(2 * sd_off_wout(NT)) * sizeof(float), stream, a);
 }
 template <int NT, int SCORE>
-static int launch_kl_adjoint_s(const AdjArgs& a, int grid, hipStream_t stream) {
-  const size_t lds_bytes = static_cast<size_t>(2 * sd_off_wout(NT)) * sizeof(float);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kl_adjoint<NT, SCORE>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL((k_kl_adjoint<NT, SCORE>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
-  return static_cast<int>(hipGetLastError());
+static int launch_kl_adjoint(const void* p, hipStream_t stream) {
+  const AdjArgs& a = *static_cast<const AdjArgs*>(p);
+  return sd_launch_kernel(k_kl_adjoint<NT, SCORE>, sd_grid(a.ntiles_b), SD_THREADS, static_cast<size_t>(2 * sd_off_wout(NT)) * sizeof(float), stream, a);
 }
-template <int NT>
-static int launch_kl_adjoint(const AdjArgs& a, int grid, hipStream_t stream) {
-  if (a.has_score == ADJ_GMM) return launch_kl_adjoint_s<NT, ADJ_GMM>(a, grid, stream);
-  if (a.has_score == ADJ_PHI4) return launch_kl_adjoint_s<NT, ADJ_PHI4>(a, grid, stream);
-  if (a.has_score == ADJ_EXT) return launch_kl_adjoint_s<NT, ADJ_EXT>(a, grid, stream);
-  return launch_kl_adjoint_s<NT, ADJ_NONE>(a, grid, stream);
-}
-#define SD_DEFINE_VJP(NT) \
-  int sd_launch_vjp_##NT(const VjpArgs& a, int grid, hipStream_t s) { return launch_ctrl_vjp<NT>(a, grid, s); } \
-  int sd_launch_adjoint_##NT(const AdjArgs& a, int grid, hipStream_t s) { return launch_kl_adjoint<NT>(a, grid, s); }

@@ -1079,10 +1079,7 @@ int sd_launch_moves(const MovesArgs& a, hipStream_t s) {
   int cpb = 64;
   while (cpb > 8 && static_cast<size_t>(cpb) * SD_MOVE_ROWS * stride * sizeof(float) > 150 * 1024) cpb /= 2;  // d > ~115: 32 chains per block
   const size_t lds = static_cast<size_t>(cpb) * SD_MOVE_ROWS * stride * sizeof(float);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_langevin_moves), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL(k_langevin_moves, dim3((a.B + cpb - 1) / cpb), dim3(64), lds, s, a, cpb);
-  return static_cast<int>(hipGetLastError());
+  return sd_launch_kernel(k_langevin_moves, (a.B + cpb - 1) / cpb, 64, lds, s, a, cpb);
 }
 int sd_launch_terminal(const TerminalArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_terminal, dim3((a.B + SD_EVAL_ROWS - 1) / SD_EVAL_ROWS), dim3(SD_EVAL_THREADS), (SD_EVAL_ROWS * (a.d | 1) + SD_EVAL_RED_FLOATS) * sizeof(float), s, a);

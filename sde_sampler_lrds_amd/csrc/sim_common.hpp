@@ -125,3 +125,33 @@ struct SimArgs {
   int ntiles;             // ceil(B / 16)
   LogregDev lr;           // in-loop logistic-regression score (ScoreCtrl on a LOGREG target, CMCD)
 };
+
+// ---- host side: launching one kernel instance -----------------------------------------------------------------------------------
+// One persistent workgroup per CU (LDS image + 2 waves/SIMD fill a CU); tiles are dealt to workgroups first, to the waves of a
+// workgroup second, so a small batch spreads over the whole chip.
+inline int sd_grid(int ntiles) { return ntiles > 256 ? 256 : (ntiles < 1 ? 1 : ntiles); }
+
+// Raise the kernel's dynamic-LDS limit to what this launch asks for, launch, and report the launch error.
+template <class... Formals, class... Actuals>
+inline int sd_launch_kernel(void (*kernel)(Formals...), int grid, int block, size_t lds_bytes, hipStream_t stream, const Actuals&... args) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
+  if (e != hipSuccess) return static_cast<int>(e);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, stream, args...);
+  return static_cast<int>(hipGetLastError());
+}
+
+// Registry of the step-loop kernel instances (gen/registry.hip, generated by build.py from its INSTANCES list).  A key is the family,
+// the feature tiles NT and the family's own template parameters after NT, in order:
+//   SIM (REF, SC, FORM, PAR)   CTRL (SC)   SPLIT (REF, FORM, PERT)   EULER (SC)   CMCD (TGT, EUBO, PAR)   VJP (GX)   ADJ (SCORE)
+// A launcher takes the family's argument block (SimArgs, CmcdArgs, VjpArgs or AdjArgs) and launches exactly that instance.
+enum { SD_FAM_SIM = 0, SD_FAM_CTRL, SD_FAM_SPLIT, SD_FAM_EULER, SD_FAM_CMCD, SD_FAM_VJP, SD_FAM_ADJ };
+constexpr uint32_t sd_key(int fam, int nt, int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0) {  // every field < 16
+  return static_cast<uint32_t>(fam) << 24 | static_cast<uint32_t>(nt) << 16 | p0 << 12 | p1 << 8 | p2 << 4 | p3;
+}
+typedef int (*sd_launcher)(const void* args, hipStream_t stream);
+struct SdKernelEntry {
+  uint32_t key;
+  sd_launcher fn;
+};
+extern const SdKernelEntry sd_registry[];  // sorted by key
+extern const int sd_registry_size;

@@ -735,39 +735,18 @@ __global__ void __launch_bounds__(SD_THREADS, SD_WAVES / 4) k_ctrl_forward(const
   }
 }
 
+// host-side launchers, one per instance (gen/, registry.hip): sdeng_api.hip select_* fixes every template parameter
 template <int NT, int SC>
-static int launch_ctrl_forward(const SimArgs& a, int grid, hipStream_t stream) {
-  const size_t lds_bytes = static_cast<size_t>(sd_lds_total_bytes(NT, false));
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctrl_forward<NT, SC>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL((k_ctrl_forward<NT, SC>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
-  return static_cast<int>(hipGetLastError());
+static int launch_ctrl_forward(const void* p, hipStream_t stream) {
+  const SimArgs& a = *static_cast<const SimArgs*>(p);
+  return sd_launch_kernel(k_ctrl_forward<NT, SC>, sd_grid(a.ntiles), SD_THREADS, static_cast<size_t>(sd_lds_total_bytes(NT, false)), stream, a);
 }
-#define SD_DEFINE_CTRL(NT, SC) \
-  int sd_launch_ctrl_##NT##_##SC(const SimArgs& a, int grid, hipStream_t s) { return launch_ctrl_forward<NT, SC>(a, grid, s); }
-
-// host-side launcher, one per instantiation (defined in gen/sim_*.hip)
 template <int NT, int REF, int SC, int FORM, int PAR>
-static int launch_simulate_par(const SimArgs& a, int grid, hipStream_t stream) {
+static int launch_simulate(const void* p, hipStream_t stream) {
+  const SimArgs& a = *static_cast<const SimArgs*>(p);
   constexpr int W = sd_waves_of<NT, REF, SC, FORM, PAR>();
   const size_t lds_bytes = static_cast<size_t>(sd_lds_total_bytes(NT, REF == RF_GAUSS || REF == RF_GMM, W)) +
                            ((SC == SC_LOGREG && a.lr.in_lds) ? sizeof(float) * sd_lr_floats(NT, a.lr.n_rows) : 0) +
                            ((REF == RF_GMM_BIG || REF == RF_GMM_FULL || REF == RF_GMM_MM) ? sizeof(float) * 2 * sd_share_buf_floats(a.ref_share) : 0);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_simulate<NT, REF, SC, FORM, PAR>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-  if (e != hipSuccess) return static_cast<int>(e);
-  hipLaunchKernelGGL((k_simulate<NT, REF, SC, FORM, PAR>), dim3(grid), dim3(64 * W), lds_bytes, stream, a);
-  return static_cast<int>(hipGetLastError());
+  return sd_launch_kernel(k_simulate<NT, REF, SC, FORM, PAR>, sd_grid(a.ntiles), 64 * W, lds_bytes, stream, a);
 }
-template <int NT, int REF, int SC, int FORM>
-static int launch_simulate(const SimArgs& a, int grid, hipStream_t stream) {
-  if constexpr (FORM == SDENG_FORM_LIN || FORM == SDENG_FORM_EM) {  // (sdeng_simulate accepts the perturbation flags on these forms only)
-    if (a.flags & (SDENG_FLAG_CTRL_NOISE | SDENG_FLAG_CTRL_DROPOUT)) return launch_simulate_par<NT, REF, SC, FORM, 2>(a, grid, stream);
-  }
-  if (a.noise_in || a.xs_out) return launch_simulate_par<NT, REF, SC, FORM, 1>(a, grid, stream);
-  return launch_simulate_par<NT, REF, SC, FORM, 0>(a, grid, stream);
-}
-
-#define SD_DEFINE_SIM(NT, REF, SC, FORM) \
-  int sd_launch_sim_##NT##_##REF##_##SC##_##FORM(const SimArgs& a, int grid, hipStream_t s) { return launch_simulate<NT, REF, SC, FORM>(a, grid, s); }

@@ -332,30 +332,10 @@ __global__ void __launch_bounds__(SD_THREADS, SD_WAVES / 4) k_simulate_split(con
   }
 }
 
-template <int NT, int REF, int FORM, bool PERT>
-static int launch_split_k(const SimArgs& a, hipStream_t stream) {
-  const size_t lds_bytes = static_cast<size_t>(sd_split_lds_bytes(NT));
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_simulate_split<NT, REF, FORM, PERT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds_bytes));
-  if (e != hipSuccess) return static_cast<int>(e);
-  int grid = (a.ntiles + 1) / 2;
-  grid = grid > 256 ? 256 : (grid < 1 ? 1 : grid);
-  hipLaunchKernelGGL((k_simulate_split<NT, REF, FORM, PERT>), dim3(grid), dim3(SD_THREADS), lds_bytes, stream, a);
-  return static_cast<int>(hipGetLastError());
+// host-side launcher of one instance (gen/split_<NT>.hip): two tiles per workgroup
+template <int NT, int REF, int FORM, int PERT>
+static int launch_split(const void* p, hipStream_t stream) {
+  const SimArgs& a = *static_cast<const SimArgs*>(p);
+  return sd_launch_kernel(k_simulate_split<NT, REF, FORM, PERT != 0>, sd_grid((a.ntiles + 1) / 2), SD_THREADS, static_cast<size_t>(sd_split_lds_bytes(NT)),
+                          stream, a);
 }
-template <int NT, int REF, int FORM>
-static int launch_split(const SimArgs& a, hipStream_t stream) {
-  if (a.flags & (SDENG_FLAG_CTRL_NOISE | SDENG_FLAG_CTRL_DROPOUT)) return launch_split_k<NT, REF, FORM, true>(a, stream);
-  return launch_split_k<NT, REF, FORM, false>(a, stream);
-}
-// one launcher per feature-tile count: reference kind and form are picked at run time
-template <int NT>
-static int launch_split_nt(const SimArgs& a, int rf, hipStream_t stream) {
-  const bool lin = a.form == SDENG_FORM_LIN;
-  if (rf == RF_NONE) return lin ? launch_split<NT, RF_NONE, SDENG_FORM_LIN>(a, stream) : launch_split<NT, RF_NONE, SDENG_FORM_EM>(a, stream);
-  if (rf == RF_GAUSS) return lin ? launch_split<NT, RF_GAUSS, SDENG_FORM_LIN>(a, stream) : launch_split<NT, RF_GAUSS, SDENG_FORM_EM>(a, stream);
-  if (rf == RF_GMM) return lin ? launch_split<NT, RF_GMM, SDENG_FORM_LIN>(a, stream) : launch_split<NT, RF_GMM, SDENG_FORM_EM>(a, stream);
-  return static_cast<int>(hipErrorInvalidValue);
-}
-#define SD_DEFINE_SPLIT(NT) \
-  int sd_launch_split_##NT(const SimArgs& a, int rf, hipStream_t s) { return launch_split_nt<NT>(a, rf, s); }
