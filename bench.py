@@ -7,12 +7,14 @@ exponential integrator, 65 536 particles x 256 steps per GPU, FourierMLP drift n
 and the log-Z / ESS reduction (the window the reference times as eval/sample_time, solver/oc.py:148-158); the inputs are the
 seed and the model.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rds_gmm|pis_phi4|cmcd_logreg]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rds_gmm|pis_phi4|cmcd_logreg] [--full]
 
 For N>1 launch with torch.distributed.run (one rank per GPU, RCCL): the particle batch is sharded (weak scaling: 65 536 particles
 per rank), no collective inside the step loop, one 36-byte all-gather for the final log-Z / ESS.
 
-Prints ONE JSON line (rank 0): the contract keys for the headline workload, plus
+Prints ONE JSON line (rank 0): the contract keys for the headline workload.  A plain run does only what they need: set-up, the
+spin-up and W warm-up passes, the K timed passes, and --dump-outputs if given (the secondary workloads' passes run then too, as
+their arrays are part of the dump, but nothing of theirs is reported).  With --full the line also holds
   roofline       what binds the step-loop kernel: the SIMD vector-issue port (`bound: valu_issue`, frac = measured port-busy share, from the
                  counter record of THIS library build) -- or, without such a record, the matrix pipe's live utilisation; plus the
                  matrix-pipe (`mfma_pipe`) and FP32-equivalent (`fp32_equiv`) figures, the issue model (`issue`) and HBM traffic (PMC)
@@ -202,8 +204,9 @@ def roofline(cfg, info, B, N, k_ms, extra_flops=0):
     return r
 
 
-def measure(cfg, device, B, N, steps, warmup, spinup, dist, rank, world, modes=4):
-    """Timed passes of one workload: W warm-up, K timed, barrier + synchronize on both sides, max over ranks."""
+def measure(cfg, device, B, N, steps, warmup, spinup, dist, rank, world, modes=4, full=True):
+    """Timed passes of one workload: W warm-up, K timed, barrier + synchronize on both sides, max over ranks.  ``full``: then also
+    the step-loop kernel's own duration and the log-Z parity block, each from passes of their own after the timed region."""
     from sde_sampler_lrds_amd import _lib as L
     from sde_sampler_lrds_amd import engine as E
     from sde_sampler_lrds_amd import parallel
@@ -256,19 +259,23 @@ def measure(cfg, device, B, N, steps, warmup, spinup, dist, rank, world, modes=4
         wt = torch.tensor([wall], device=device)
         dist.all_reduce(wt, op=dist.ReduceOp.MAX)
         wall = wt.item()
+    m = dict(cfg=cfg, B=B, N=N, info=info, ts=ts, wall=wall, steps=steps, value=world * B * N * steps / wall, ms_per_step=1e3 * wall / steps,
+             res=results[-1], seed=1, outputs=outputs)
+    if not full:
+        return m
     # step-loop kernel duration: HIP events recorded by sdeng_simulate around that launch, on the launch stream
     samples = [ev.elapsed_ms()]
     for _ in range(min(5, steps)):
         loss.simulate(ts, x0, *args, **kw)
         samples.append(ev.elapsed_ms())
-    k_ms = sum(samples) / len(samples)
+    m["kernel_ms"] = sum(samples) / len(samples)
     # the log-Z parity block (identical seeds), outside the timed region
     loss.particle0 = 0
     loss.timing_events = None
     hx, hrnd, _ = loss.simulate(ts, E.InitialDraw(prior, Z_BLOCK, device), *args, **kw)
     torch.cuda.synchronize()
-    return dict(cfg=cfg, B=B, N=N, info=info, ts=ts, wall=wall, steps=steps, value=world * B * N * steps / wall, ms_per_step=1e3 * wall / steps,
-                kernel_ms=k_ms, res=results[-1], hip_block=(hx, hrnd), seed=1, outputs=outputs)
+    m["hip_block"] = (hx, hrnd)
+    return m
 
 
 DUMP_ROWS = 16384              # particles of the fixed sample dumped for the secondary workloads
@@ -344,8 +351,12 @@ def main():
     ap.add_argument("--particles", type=int, default=None, help="per GPU (default: the workload's BASELINE size)")
     ap.add_argument("--sde-steps", type=int, default=None)
     ap.add_argument("--modes", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline and kernel time, log-Z parity against the CPU "
+                         "oracle, CPU baseline, the secondary workloads (configs[2], configs[3]) with the same items")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="leave out the secondary workloads (with --full; and from --dump-outputs)")
     ap.add_argument("--spinup", type=float, default=0.3, help="seconds of untimed passes before the warm-up (clock ramp)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the arrays the last timed pass returned (x_N, rnd, estimators) as DIR/<name>.npy (rank 0)")
@@ -370,15 +381,13 @@ def main():
         B = a.particles
     if a.sde_steps is not None:
         N = a.sde_steps
-    head = measure(wl, device, B, N, a.steps, a.warmup, a.spinup, dist, rank, world, modes=a.modes)
+    head = measure(wl, device, B, N, a.steps, a.warmup, a.spinup, dist, rank, world, modes=a.modes, full=a.full)
     others = []
-    if world == 1 and not a.no_other_configs and wl == "rds_gmm":
+    # the secondary workloads: reported with --full; their passes also run for --dump-outputs, whose dump holds their arrays
+    if world == 1 and not a.no_other_configs and wl == "rds_gmm" and (a.full or a.dump_outputs):
         for cfg in ("pis_phi4", "cmcd_logreg"):
-            others.append(measure(cfg, device, *FULL_SIZE[cfg], a.steps, a.warmup, a.spinup, None, 0, 1))
+            others.append(measure(cfg, device, *FULL_SIZE[cfg], a.steps, a.warmup, a.spinup, None, 0, 1, full=a.full))
     if rank == 0:
-        with_cpu = world == 1 and not a.no_cpu_baseline
-        chunks = {"rds_gmm": 8192, "pis_phi4": 4096, "cmcd_logreg": 2048}
-        e = config_entry(head, 15.0, chunks[wl], with_cpu)
         desc = {"rds_gmm": f"ManyModes d=128 K={a.modes}, RDS gmm-ref, VP(0.1,10), EI integrator",
                 "pis_phi4": "PhiFour d=100, PIS target-informed drift, EM integrator",
                 "cmcd_logreg": "LogisticRegression d=61 (sonar-shaped synthetic design matrix), CMCD lv-loss sampler"}[wl]
@@ -388,16 +397,20 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{desc}, {B} particles x {N} steps per GPU, FourierMLP(4x64) drift, x0 and noise drawn by the engine (Philox)",
                        "name": wl, "particles_per_gpu": B, "sde_steps": N, "parallelism": f"particle-sharded x{world}"},
-            "log_z_abs_err": e["log_z_abs_err"], "parity": e["parity"], "path": e["path"],
-            "log_norm_const_is": e["log_norm_const_is"], "ess": e["ess"], "spinup_s": a.spinup, "roofline": e["roofline"],
-            "library_digest": library_digest(),
+            "path": path_of(wl, head["info"]), "log_norm_const_is": head["res"]["log_norm_const_is"], "ess": head["res"]["ess"],
+            "spinup_s": a.spinup, "library_digest": library_digest(),
         }
-        out["roofline"]["kernel"] = e["path"].split(":")[0] + " (one launch = all sde_steps of the batch)"
-        if "cpu_baseline" in e:
-            out["cpu_baseline"] = e["cpu_baseline"]
-            out["speedup_vs_cpu"] = e["speedup_vs_cpu"]
-        if others:
-            out["other_configs"] = [config_entry(m, 8.0, chunks[m["cfg"]], with_cpu) for m in others]
+        if a.full:
+            with_cpu = world == 1 and not a.no_cpu_baseline
+            chunks = {"rds_gmm": 8192, "pis_phi4": 4096, "cmcd_logreg": 2048}
+            e = config_entry(head, 15.0, chunks[wl], with_cpu)
+            out.update(log_z_abs_err=e["log_z_abs_err"], parity=e["parity"], roofline=e["roofline"])
+            out["roofline"]["kernel"] = e["path"].split(":")[0] + " (one launch = all sde_steps of the batch)"
+            if "cpu_baseline" in e:
+                out["cpu_baseline"] = e["cpu_baseline"]
+                out["speedup_vs_cpu"] = e["speedup_vs_cpu"]
+            if others:
+                out["other_configs"] = [config_entry(m, 8.0, chunks[m["cfg"]], with_cpu) for m in others]
         if a.dump_outputs:
             out["dumped_outputs"] = dump_outputs(a.dump_outputs, [head] + others)
         print(json.dumps(out))

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_under_torch_distributed_run(gpu):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SDENG_BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--spinup", "0.05"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs", "--spinup", "0.05"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -34,7 +34,8 @@ def test_bench_under_torch_distributed_run(gpu):
 @pytest.mark.gpu
 def test_bench_dump_outputs_are_reproducible(gpu, tmp_path):
     """--dump-outputs writes the arrays of the last timed pass; two runs with the same arguments dump the same values (fixed seeds,
-    deterministic kernels), and --steps sets the number of timed passes."""
+    deterministic kernels), and --steps sets the number of timed passes.  Without --full the line holds nothing that needs passes or
+    CPU work of its own."""
     import numpy as np
     dumps = []
     for run in ("a", "b"):
@@ -47,6 +48,7 @@ def test_bench_dump_outputs_are_reproducible(gpu, tmp_path):
         assert len(lines) == 1, r.stdout[-2000:]
         j = json.loads(lines[0])
         assert j["steps"] == 2 and j["ms_per_step"] > 0.0
+        assert not {"roofline", "log_z_abs_err", "parity", "cpu_baseline", "other_configs"} & set(j), sorted(j)
         assert sorted(os.listdir(out)) == j["dumped_outputs"]["files"]
         dumps.append({f: np.load(out / f) for f in j["dumped_outputs"]["files"]})
     a, b = dumps
