@@ -366,6 +366,42 @@ size_t sdeng_langevin_moves_workspace_bytes(const sdeng_dist* prior, const sdeng
  * 235-239, 709-713; distr/delta.py:27-31). */
 int sdeng_sample_x0(const sdeng_dist* dist, uint64_t seed, int64_t particle0, int32_t B, int32_t d, float* out, void* stream);
 
+/* Sample-quality metrics of the reference's evaluation layer (eval/metrics.py:173-191 applies them to the samples of every model).
+ *
+ * sdeng_sinkhorn: the entropy-regularised p-Wasserstein distance of Sinkhorn.compute (eval/sinkhorn.py:64-177, written there on pykeops
+ * lazy tensors) between x [n,d] and y [m,d]:  M_ij = (sum_k |x_ik - y_jk|^p)^(1/p), p in {1, 2} (else SDENG_E_UNSUPPORTED);
+ * w_x [n], w_y [m] or both NULL = uniform 1/n and (1/m)(n/m) (:123-126);  u = 0, v = eps log w_y;  per iteration
+ *     u_i = eps (log w_x,i - LSE_j((v_j - M_ij) / eps)),   v_j = eps (log w_y,j - LSE_i((u_i - M_ij) / eps))  with the new u,
+ * until max|du| < stop_thresh and max|dv| < stop_thresh or max_iters iterations (:143-160); then
+ * distance = sum_ij P_ij M_ij with P_ij = exp((u_i + v_j - M_ij) / eps), corr_x_to_y[i] = argmax_j P_ij, corr_y_to_x[j] = argmax_i P_ij
+ * (:162-171).  M is built once from differences accumulated in double and kept as fp32 in the workspace when the workspace has room for
+ * it (sdeng_sinkhorn_workspace_bytes(n, m, d, 1)) and n m 4 <= SDENG_SINKHORN_MATRIX_MAX_BYTES: each half-iteration is then one
+ * streaming pass over it.  With the smaller workspace (..., 0), or beyond that size, every pass recomputes the costs from x and y --
+ * same arithmetic, same result, O(n + m) memory.  u, v and the exponents are double inside; u_out [n], v_out [m] (optional) are fp32.
+ * One 16-byte read-back per iteration (the stop test): the call returns with the stream synchronised and `result` (host memory) filled.
+ * Reductions run in a fixed order: two calls on the same input agree bit for bit. */
+#define SDENG_SINKHORN_MATRIX_MAX_BYTES (1ull << 30)
+typedef struct sdeng_sinkhorn_result {
+  double distance;
+  double max_err_u, max_err_v; /* max |change| of u and v in the last iteration        */
+  int32_t iters;               /* iterations run                                        */
+  int32_t materialised;        /* 1: the cost matrix was kept in the workspace          */
+} sdeng_sinkhorn_result;
+int sdeng_sinkhorn(const float* x, const float* y, int32_t n, int32_t m, int32_t d, int32_t p, double eps, int32_t max_iters,
+                   double stop_thresh, const float* w_x, const float* w_y, float* u_out, float* v_out, int32_t* corr_x_to_y,
+                   int32_t* corr_y_to_x, sdeng_sinkhorn_result* result, void* workspace, size_t workspace_bytes, void* stream);
+size_t sdeng_sinkhorn_workspace_bytes(int32_t n, int32_t m, int32_t d, int32_t materialise);
+
+/* sdeng_mmd_median: mmd_median(X, Y) of additions/mmd.py:30-59 for X, Y [n,d] (n == m >= 2 as asserted there) without its n x n
+ * matrices.  The bandwidth is the lower median (torch.median: rank (N - 1) / 2) of the N = n (2n - 1) squared distances
+ * {XX, i < j} + {YY, i < j} + {XY, all} -- the pairs i < j of the pooled sample -- found exactly by a three-pass radix selection over the
+ * bit patterns of the fp32 distances (each pass recomputes them); then the Gaussian-kernel sums of :47-56 in double and
+ * out[0] = sqrt(max(1e-20, mmd^2)), out[1] = bandwidth_sq (device memory, 2 floats).  Workspace: O(n) (48 KB of counters and
+ * 6 KB of partial sums per 1024 rows).  No read-back; integer counters are the only atomics, so reruns agree bit for bit. */
+int sdeng_mmd_median(const float* X, const float* Y, int32_t n, int32_t m, int32_t d, float* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t sdeng_mmd_median_workspace_bytes(int32_t n, int32_t d);
+
 #ifdef __cplusplus
 }
 #endif

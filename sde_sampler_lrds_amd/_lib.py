@@ -62,6 +62,11 @@ class Desc(C.Structure):
                 ("ev_start", _fp), ("ev_stop", _fp), ("x0_dist", Dist), ("x0_out", _fp)]
 
 
+class SinkhornResult(C.Structure):  # sdeng_sinkhorn_result (include/sdeng.h)
+    _fields_ = [("distance", C.c_double), ("max_err_u", C.c_double), ("max_err_v", C.c_double), ("iters", C.c_int32),
+                ("materialised", C.c_int32)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"sdeng error {code}: {msg}")
@@ -74,7 +79,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsdeng.so
 EXPORTS = ["sdeng_abi_version", "sdeng_last_error", "sdeng_workspace_bytes", "sdeng_simulate", "sdeng_logz",
            "sdeng_logz_workspace_bytes", "sdeng_ctrl_forward", "sdeng_dist_eval", "sdeng_dist_workspace_bytes",
            "sdeng_philox_normal", "sdeng_philox_normal_steps", "sdeng_sample_x0", "sdeng_ctrl_vjp", "sdeng_ctrl_vjp_workspace_bytes",
-           "sdeng_langevin_moves", "sdeng_langevin_moves_workspace_bytes", "sdeng_kl_adjoint", "sdeng_kl_adjoint_workspace_bytes"]
+           "sdeng_langevin_moves", "sdeng_langevin_moves_workspace_bytes", "sdeng_kl_adjoint", "sdeng_kl_adjoint_workspace_bytes",
+           "sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes"]
 
 
 def lib() -> C.CDLL:
@@ -122,6 +128,15 @@ def lib() -> C.CDLL:
         [C.c_void_p] * 7 + [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.sdeng_langevin_moves_workspace_bytes.restype = C.c_size_t
     L.sdeng_langevin_moves_workspace_bytes.argtypes = [C.POINTER(Dist), C.POINTER(Dist), C.c_int32]
+    L.sdeng_sinkhorn.restype = C.c_int
+    L.sdeng_sinkhorn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double] + \
+        [C.c_void_p] * 6 + [C.POINTER(SinkhornResult), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdeng_sinkhorn_workspace_bytes.restype = C.c_size_t
+    L.sdeng_sinkhorn_workspace_bytes.argtypes = [C.c_int32] * 4
+    L.sdeng_mmd_median.restype = C.c_int
+    L.sdeng_mmd_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdeng_mmd_median_workspace_bytes.restype = C.c_size_t
+    L.sdeng_mmd_median_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     if L.sdeng_abi_version() != ABI_VERSION:
         raise ImportError(f"libsdeng.so ABI {L.sdeng_abi_version()} != binding ABI {ABI_VERSION}")
     _LIB = L

@@ -28,9 +28,10 @@ def evaluate_eubo(trainable, results, compute_eubo_last_arg, use_ema):
 class TrainableWrapper:
     """additions/hacking.py:36-102 (evaluation side)."""
 
-    def __init__(self, trainable, verbose=True):
+    def __init__(self, trainable, verbose=True, sample_metrics=False):
         self.trainable = trainable
         self.verbose = verbose
+        self.sample_metrics = sample_metrics  # run() / evaluate() also report eval/metrics.py:get_metrics (Trainable.evaluate(log=True))
 
     def run(self, keep_training_metrics=False):
         """additions/hacking.py:43-66: train for the remaining steps (log-variance training runs on the HIP step loop; KL
@@ -64,4 +65,6 @@ class TrainableWrapper:
         t = self.trainable
         use_ema_ = getattr(t, "use_ema", False) and use_ema
         results = t.compute_results(use_ema=use_ema_)
+        if self.sample_metrics:
+            t.get_metrics(results)
         return self.compute_results_eubo(results, use_ema=use_ema_)

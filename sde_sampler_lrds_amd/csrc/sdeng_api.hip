@@ -17,6 +17,7 @@
 #include "sim_kernel.hpp"
 #include "cmcd_kernel.hpp"
 #include "grad_kernel.hpp"
+#include "metric_kernels.hpp"
 
 int sd_launch_logreg_images(const float* X, const float* y, int n, int dw, int NT, float* image, float* y_pad, hipStream_t s);
 int sd_launch_pack_square(const float* P, const float* loc, int d, int NT, float* out, float* loc_pad, hipStream_t s);
@@ -979,5 +980,56 @@ extern "C" int sdeng_philox_normal_steps(uint64_t seed, int32_t step0, int32_t n
   if (B == 0 || n_steps == 0) return 0;
   const Seed sd = split_seed(seed);
   SD_HIP(sd_launch_philox(sd.lo, sd.hi, step0, n_steps, particle0, B, d, stream_id, out, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+// ---- sample-quality metrics (eval/sinkhorn.py, additions/mmd.py) ---------------------------------------------------------------------
+static bool sk_fits(int32_t n, int32_t m) { return sizeof(float) * static_cast<size_t>(n) * m <= SDENG_SINKHORN_MATRIX_MAX_BYTES; }
+extern "C" size_t sdeng_sinkhorn_workspace_bytes(int32_t n, int32_t m, int32_t d, int32_t materialise) {
+  if (n < 1 || m < 1 || d < 1) return 0;
+  const SkLayout L = sd_sk_layout(n, m);
+  return materialise && sk_fits(n, m) ? L.total_bytes : L.small_bytes;
+}
+extern "C" int sdeng_sinkhorn(const float* x, const float* y, int32_t n, int32_t m, int32_t d, int32_t p, double eps, int32_t max_iters,
+                              double stop_thresh, const float* w_x, const float* w_y, float* u_out, float* v_out, int32_t* corr_x_to_y,
+                              int32_t* corr_y_to_x, sdeng_sinkhorn_result* result, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !y || !result || n < 1 || m < 1 || d < 1 || max_iters < 1 || !(eps > 0.0)) return fail(SDENG_E_INVALID, "sinkhorn: bad argument");
+  if ((w_x == nullptr) != (w_y == nullptr)) return fail(SDENG_E_INVALID, "sinkhorn: give both weight vectors, or neither");
+  if (p != 1 && p != 2) return fail(SDENG_E_UNSUPPORTED, "sinkhorn: p in {1, 2}, got %d", p);
+  const SkLayout L = sd_sk_layout(n, m);
+  if (!workspace || workspace_bytes < L.small_bytes) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", workspace_bytes, L.small_bytes);
+  char* ws = static_cast<char*>(workspace);
+  SkArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.w_x = w_x; a.w_y = w_y; a.n = n; a.m = m; a.d = d; a.p = p; a.eps = eps; a.inv_eps = 1.0 / eps;
+  a.u = reinterpret_cast<double*>(ws + L.u); a.v = reinterpret_cast<double*>(ws + L.v);
+  a.loga = reinterpret_cast<double*>(ws + L.loga); a.logb = reinterpret_cast<double*>(ws + L.logb);
+  a.du = reinterpret_cast<double*>(ws + L.du); a.dv = reinterpret_cast<double*>(ws + L.dv);
+  a.rowsum = reinterpret_cast<double*>(ws + L.rowsum); a.part = reinterpret_cast<double*>(ws + L.part);
+  a.part_idx = reinterpret_cast<int*>(ws + L.part_idx); a.errs = reinterpret_cast<double*>(ws + L.errs);
+  a.chunks = L.chunks; a.rows_per_chunk = L.rows_per_chunk;
+  a.u_out = u_out; a.v_out = v_out; a.corr_xy = corr_x_to_y; a.corr_yx = corr_y_to_x;
+  float* M = sk_fits(n, m) && workspace_bytes >= L.total_bytes ? reinterpret_cast<float*>(ws + L.M) : nullptr;
+  SD_HIP(sd_run_sinkhorn(a, M, max_iters, stop_thresh, result, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" size_t sdeng_mmd_median_workspace_bytes(int32_t n, int32_t d) {
+  if (n < 2 || d < 1) return 0;
+  return sd_mmd_layout(n).total_bytes;
+}
+extern "C" int sdeng_mmd_median(const float* X, const float* Y, int32_t n, int32_t m, int32_t d, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  if (!X || !Y || !out || d < 1) return fail(SDENG_E_INVALID, "mmd_median: bad argument");
+  if (n != m || n < 2) return fail(SDENG_E_INVALID, "mmd_median: n == m >= 2 (additions/mmd.py:33-36), got %d and %d", n, m);
+  if (n > (1 << 29)) return fail(SDENG_E_UNSUPPORTED, "mmd_median: n <= 2^29");
+  const MmdLayout L = sd_mmd_layout(n);
+  if (!workspace || workspace_bytes < L.total_bytes) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", workspace_bytes, L.total_bytes);
+  char* ws = static_cast<char*>(workspace);
+  MmdArgs a;
+  a.X = X; a.Y = Y; a.n = n; a.d = d; a.tiles = L.tiles; a.groups = L.groups;
+  a.hist = reinterpret_cast<unsigned long long*>(ws + L.hist); a.state = reinterpret_cast<unsigned long long*>(ws + L.state);
+  a.part = reinterpret_cast<double*>(ws + L.part); a.out = out;
+  SD_HIP(sd_run_mmd_median(a, static_cast<hipStream_t>(stream)));
   return 0;
 }

@@ -4,6 +4,8 @@ autograd).  The simulate path never calls these: it reads the parameters through
 evaluates log-densities and scores in HIP (csrc/prep_kernels.hip, csrc/sim_device.hpp)."""
 from __future__ import annotations
 
+import math
+
 import torch
 
 
@@ -71,6 +73,48 @@ class Distribution(torch.nn.Module):
 
     def forward(self, x):
         return self.unnorm_log_prob(x)
+
+
+class ModeWeightMetrics:
+    """The sample-based diagnostics of the multi-modal targets (``distr/gauss.py:245-293``, ``distr/rings.py:111-160``,
+    ``distr/checkerboard.py:93-140``): entropy of the empirical mode weights, their KL / TV distance to the true weights and the share
+    of forgotten modes.  A class provides ``compute_mode_count(samples)`` and ``_true_mode_probs()``; ``_mode_hist`` turns the counts
+    into the empirical weights.  Host-side torch on the samples' device."""
+
+    def has_entropy(self):
+        return True
+
+    def _mode_hist(self, counts):
+        return counts.flatten() / counts.sum()
+
+    def _true_hist(self, like):
+        probs = self._true_mode_probs().to(like.device).flatten()
+        return probs / probs.sum()
+
+    def entropy(self, samples, counts=None):
+        if counts is None:
+            counts = self.compute_mode_count(samples)
+        hist = self._mode_hist(counts)
+        return -torch.sum(hist * (torch.log(hist) / math.log(counts.shape[0])))
+
+    def kl_weights(self, samples, counts=None):
+        if counts is None:
+            counts = self.compute_mode_count(samples)
+        hist = self._mode_hist(counts)
+        true_hist = self._true_hist(hist)
+        return torch.sum(true_hist * torch.log(true_hist / hist))
+
+    def tv_weights(self, samples, counts=None):
+        if counts is None:
+            counts = self.compute_mode_count(samples)
+        hist = self._mode_hist(counts)
+        return torch.sum(torch.abs(hist - self._true_hist(hist)))
+
+    def compute_forgotten_modes(self, samples, tol=0.05, counts=None):
+        if counts is None:
+            counts = self.compute_mode_count(samples)
+        hist = self._mode_hist(counts)
+        return torch.sum(hist < tol * self._true_hist(hist).min()) / self.n_mixtures
 
 
 def sample_uniform(domain: torch.Tensor, batchsize: int = 1) -> torch.Tensor:

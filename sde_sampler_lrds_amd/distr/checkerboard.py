@@ -2,13 +2,14 @@
 squares of side 2 on alternating cells of the domain [-4, -4 + 2 width] x [-4, 4], the even-numbered squares three times as likely as
 the odd ones (``unequilibrated=True``).  Its log-density is -inf outside every square, and its score is zero everywhere (the
 reference returns zeros instead of differentiating).  Host-side torch methods only; the simulate path reads the corner tables and
-the per-square log-density through ``engine.dist_desc`` and evaluates both in HIP.  The sample-based diagnostics of the reference's
-eval layer (mode histogram, entropy, KL / TV of the mode weights, forgotten modes) are not on this path."""
+the per-square log-density through ``engine.dist_desc`` and evaluates both in HIP.  The sample-based diagnostics that
+``eval/metrics.py`` reports (mode histogram, entropy, KL / TV of the mode weights, forgotten modes; reference :93-140) are host-side
+torch on the samples' device."""
 from __future__ import annotations
 
 import torch
 
-from .base import Distribution
+from .base import Distribution, ModeWeightMetrics
 
 
 def square_corners(width: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -23,7 +24,7 @@ def square_corners(width: int) -> tuple[torch.Tensor, torch.Tensor]:
     return torch.tensor(xs, dtype=torch.float32), torch.tensor(ys, dtype=torch.float32)
 
 
-class Checkerboard(Distribution):
+class Checkerboard(ModeWeightMetrics, Distribution):
     def __init__(self, dim: int = 2, width: int = 4, unequilibrated: bool = True, n_reference_samples: int = int(1e5), **kwargs):
         if dim != 2:
             raise ValueError("The checkerboard is two-dimensional.")
@@ -58,5 +59,23 @@ class Checkerboard(Distribution):
     def score(self, x: torch.Tensor, create_graph=False) -> torch.Tensor:
         return torch.zeros_like(x)
 
-    def has_entropy(self):
-        return True
+    def compute_mode_count(self, samples):
+        """Samples per cell of the 4 x ``width`` grid over the domain, rows = y bands from the bottom (reference :97-100: the
+        transposed ``torch.histogramdd`` of the samples with bins (width, 4) over the domain; samples outside it are dropped)."""
+        dom = self.domain.to(samples.device)
+        lo, hi = dom[:, 0], dom[:, 1]
+        bins = torch.tensor([self.width, 4], device=samples.device)
+        inside = ((samples >= lo) & (samples <= hi)).all(dim=-1)
+        cell = ((samples - lo) / (hi - lo) * bins).floor().long()
+        cell = torch.minimum(cell.clamp_(min=0), bins - 1)  # the upper edges belong to the last cells
+        flat = (cell[:, 1] * self.width + cell[:, 0])[inside]
+        return torch.bincount(flat, minlength=4 * self.width).to(torch.float32).view(4, self.width)
+
+    def _mode_hist(self, counts):
+        """The cells that carry mass, in the reference's order (its ``hist_mask``, :52-57), over ALL counted samples."""
+        cols = torch.arange(self.width, device=counts.device)
+        mask = torch.stack([cols % 2 == 0, cols % 2 == 1, cols % 2 == 0, cols % 2 == 1], dim=0)
+        return counts[mask].flatten() / counts.sum()
+
+    def _true_mode_probs(self):
+        return self.weights / self.weights.sum()

@@ -10,7 +10,7 @@ from numbers import Number
 import torch
 from torch import distributions as D
 
-from .base import Distribution
+from .base import Distribution, ModeWeightMetrics
 
 
 def log_prob_gaussian(x, mean, variance):
@@ -58,7 +58,7 @@ def score_mog_full(x, weights, means, covariances, precisions=None, covariances_
     return -torch.sum(p.unsqueeze(-1) * ptd, dim=1)
 
 
-class GMMFull(Distribution):
+class GMMFull(ModeWeightMetrics, Distribution):
     """Mixture of full-covariance Gaussians (distr/gauss.py GMMFull): what a full-covariance reference is at t = 0.  Only the
     log-density and score are needed on the simulate path (terminal cost); they are host-side torch."""
 
@@ -79,6 +79,22 @@ class GMMFull(Distribution):
 
     def score(self, x, *args, **kwargs):
         return score_mog_full(x, self.mixture_weights, self.loc, None, precisions=self.prec, covariances_log_det=self.cov_log_det)
+
+    # upstream's GMMFull is a GMM and inherits its mode-weight diagnostics (:245-293)
+    @property
+    def n_mixtures(self):
+        return self.loc.shape[0]
+
+    def has_entropy(self):
+        return self.n_mixtures > 1
+
+    def compute_mode_count(self, samples):
+        lp = log_prob_gaussian_full(samples, self.loc.to(samples.device), None, precisions=self.prec.to(samples.device),
+                                    covariances_log_det=self.cov_log_det.to(samples.device))
+        return torch.bincount(torch.argmax(lp, dim=-1), minlength=self.n_mixtures).to(torch.float32)
+
+    def _true_mode_probs(self):
+        return self.mixture_weights
 
     def sample(self, shape=None):
         comp = D.Categorical(self.mixture_weights).sample(torch.Size(shape or ()))
@@ -103,8 +119,13 @@ class TwoModesFull(GMMFull):
         cov = torch.matmul(q, torch.matmul(torch.diag(diag), q.T))
         super().__init__(dim=dim, loc=loc, cov=torch.stack([cov, cov.clone()]), mixture_weights=torch.FloatTensor([2.0, 1.0]), **kwargs)
 
+    def compute_mode_weight(self, samples):
+        """Share (in percent) of the samples on the first, heavier mode (reference :455-458, :508-511, :555-558)."""
+        counts = self.compute_mode_count(samples)
+        return 100.0 * counts[0] / counts.sum()
 
-class GMM(Distribution):
+
+class GMM(ModeWeightMetrics, Distribution):
     def __init__(self, dim=2, loc=None, scale=None, mixture_weights=None, n_reference_samples=int(1e7), name=None,
                  domain_scale=5, domain_tol=1e-5, **kwargs):
         super().__init__(dim=dim, log_norm_const=0.0, n_reference_samples=n_reference_samples, **kwargs)
@@ -153,6 +174,15 @@ class GMM(Distribution):
     def has_entropy(self):
         return self.n_mixtures > 1
 
+    def compute_mode_count(self, samples):
+        """Samples per mode, a sample belonging to the component under which it is most likely (reference :249-256)."""
+        comp = D.Independent(D.Normal(self.loc.to(samples.device), self.scale.to(samples.device)), 1)
+        idx = torch.argmax(comp.log_prob(samples.unsqueeze(1)), dim=-1)
+        return torch.bincount(idx, minlength=self.n_mixtures).to(torch.float32)
+
+    def _true_mode_probs(self):
+        return self.mixture_weights / self.mixture_weights.sum()
+
 
 class TwoModes(GMM):
     """(2/3) N(-a 1, C) + (1/3) N(+a 1, C), diagonal C (reference :422-466)."""
@@ -169,6 +199,11 @@ class TwoModes(GMM):
             scale = torch.sqrt(0.05 * torch.logspace(lo, 0.0, dim)).unsqueeze(0).expand(2, -1)
         super().__init__(dim=dim, loc=loc, scale=scale, mixture_weights=torch.FloatTensor([2.0, 1.0]), **kwargs)
 
+    def compute_mode_weight(self, samples):
+        """Share (in percent) of the samples on the first, heavier mode (reference :455-458, :508-511, :555-558)."""
+        counts = self.compute_mode_count(samples)
+        return 100.0 * counts[0] / counts.sum()
+
 
 class BracketTwoModes(GMM):
     """(2/3) N(-a 1, C_1) + (1/3) N(+a 1, C_2) with (C_1)_i = (C_2)_(dim-i) on a linear variance ladder (reference :522-553)."""
@@ -179,6 +214,11 @@ class BracketTwoModes(GMM):
         scale = torch.sqrt(torch.stack([ladder, torch.flip(ladder, dims=(0,))]))
         weights = torch.ones((2,)) / 2.0 if equilibrated else torch.FloatTensor([2, 1]) / 2.0
         super().__init__(dim=dim, loc=loc, scale=scale, mixture_weights=weights, **kwargs)
+
+    def compute_mode_weight(self, samples):
+        """Share (in percent) of the samples on the first, heavier mode (reference :455-458, :508-511, :555-558)."""
+        counts = self.compute_mode_count(samples)
+        return 100.0 * counts[0] / counts.sum()
 
 
 class ManyModes(GMM):

@@ -31,3 +31,8 @@ class PhiFour(Distribution):
 
     def score(self, x, *args, **kwargs):
         return -self.beta * self.grad_U(x)
+
+    def compute_phi_four_weight(self, samples):
+        """Ratio of the mass of the two wells, told apart by the sign of the middle site (reference :124-126)."""
+        mask = (samples[:, int(self.dim / 2)] > 0).float().mean()
+        return (1.0 - mask) / mask

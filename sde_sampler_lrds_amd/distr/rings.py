@@ -1,5 +1,5 @@
-"""2-D rings target (mirror of ``sde_sampler/distr/rings.py:38-121``; the sample-based diagnostics of :123-148 -- mode counts, entropy,
-KL of the mode weights -- belong to the reference's eval/ layer and are not on this path): a Gaussian mixture over the radius times a
+"""2-D rings target (mirror of ``sde_sampler/distr/rings.py:38-160``, with the sample-based diagnostics of :111-160 -- mode counts, entropy,
+KL / TV of the mode weights, forgotten modes -- that ``eval/metrics.py`` reports): a Gaussian mixture over the radius times a
 uniform angle.  Host-side torch methods only; the simulate path reads (radiuses, mixture probs, scale) through
 ``engine.dist_desc`` and evaluates log-density and score in HIP."""
 from __future__ import annotations
@@ -8,11 +8,11 @@ import math
 
 import torch
 
-from .base import Distribution
+from .base import Distribution, ModeWeightMetrics
 from .gauss import score_mog
 
 
-class Rings(Distribution):
+class Rings(ModeWeightMetrics, Distribution):
     def __init__(self, dim: int = 2, lower_rad: float = 1.0, upper_rad: float = 5.0, num_rad: int = 3, scale: float = 0.1,
                  equilibrated: bool = False, n_reference_samples: int = int(1e6), domain_tol: float = 5.0, **kwargs):
         if dim != 2:
@@ -60,3 +60,12 @@ class Rings(Distribution):
     def score(self, x, eps=1e-7, **kwargs):
         norm_x = torch.linalg.norm(x, dim=-1, keepdim=True) + eps
         return x * ((self.score_radius(norm_x) / norm_x) - (1.0 / torch.square(norm_x)))
+
+    def compute_mode_count(self, samples):
+        """Samples per ring: the ring whose squared radius is nearest to the sample's (reference :115-123)."""
+        r_sq = torch.square(samples[:, 0]) + torch.square(samples[:, 1])
+        idx = torch.argmin(torch.abs(r_sq.unsqueeze(-1) - torch.square(self.radiuses.to(samples.device))), dim=-1)
+        return torch.bincount(idx, minlength=self.n_mixtures).to(torch.float32)
+
+    def _true_mode_probs(self):
+        return self.radius_dist.mixture_distribution.probs

@@ -712,6 +712,45 @@ def dist_eval(dist, x: torch.Tensor, want_logp=True, want_score=True):
     return logp, score
 
 
+def sinkhorn(x: torch.Tensor, y: torch.Tensor, w_x=None, w_y=None, p=2, eps=1e-3, max_iters=100, stop_thresh=1e-5, materialise=True):
+    """sdeng_sinkhorn: the entropy-regularised p-Wasserstein distance between the clouds x [n,d] and y [m,d] (eval/sinkhorn.py:64-177).
+    Returns a dict: distance (0-d float32 tensor), corr_x_to_y [n], corr_y_to_x [m] (int64), u [n], v [m], iters, max_err_u, max_err_v,
+    materialised (the cost matrix was kept in the workspace; ``materialise=False`` asks for the O(n + m) workspace, whose passes
+    recompute the costs -- same result)."""
+    require_gpu(x)
+    require_gpu(y)
+    lib = L.lib()
+    device = x.device
+    xin, yin = x.detach().to(torch.float32).contiguous(), y.detach().to(device, torch.float32).contiguous()
+    (n, d), m = xin.shape, yin.shape[0]
+    wx = None if w_x is None else w_x.detach().to(device, torch.float32).contiguous()
+    wy = None if w_y is None else w_y.detach().to(device, torch.float32).contiguous()
+    u, v = torch.empty(n, dtype=torch.float32, device=device), torch.empty(m, dtype=torch.float32, device=device)
+    cxy, cyx = torch.empty(n, dtype=torch.int32, device=device), torch.empty(m, dtype=torch.int32, device=device)
+    ws = torch.empty(max(lib.sdeng_sinkhorn_workspace_bytes(n, m, d, 1 if materialise else 0), 16), dtype=torch.uint8, device=device)
+    res = L.SinkhornResult()
+    L.check(lib.sdeng_sinkhorn(xin.data_ptr(), yin.data_ptr(), n, m, d, int(p), float(eps), int(max_iters), float(stop_thresh),
+                               wx.data_ptr() if wx is not None else None, wy.data_ptr() if wy is not None else None, u.data_ptr(),
+                               v.data_ptr(), cxy.data_ptr(), cyx.data_ptr(), C.byref(res), ws.data_ptr(), ws.numel(), _stream_ptr(device)))
+    return {"distance": torch.tensor(res.distance, dtype=torch.float32, device=device), "corr_x_to_y": cxy.long(), "corr_y_to_x": cyx.long(),
+            "u": u, "v": v, "iters": res.iters, "max_err_u": res.max_err_u, "max_err_v": res.max_err_v, "materialised": bool(res.materialised)}
+
+
+def mmd_median(X: torch.Tensor, Y: torch.Tensor):
+    """sdeng_mmd_median: (mmd, bandwidth_sq) as 0-d float32 tensors -- the MMD with a Gaussian kernel whose bandwidth is the exact
+    lower median of the pooled squared distances (additions/mmd.py:30-59), without an n x n matrix."""
+    require_gpu(X)
+    require_gpu(Y)
+    lib = L.lib()
+    device = X.device
+    xin, yin = X.detach().to(torch.float32).contiguous(), Y.detach().to(device, torch.float32).contiguous()
+    (n, d), m = xin.shape, yin.shape[0]
+    out = torch.empty(2, dtype=torch.float32, device=device)
+    ws = torch.empty(max(lib.sdeng_mmd_median_workspace_bytes(n, d), 16), dtype=torch.uint8, device=device)
+    L.check(lib.sdeng_mmd_median(xin.data_ptr(), yin.data_ptr(), n, m, d, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(device)))
+    return out[0], out[1]
+
+
 def langevin_moves(target, prior, x, lp, grad, step, n_moves, *, t=None, keep_from=0, unadjusted=False, target_acceptance=0.0, noise="torch",
                    seed=0, chain0=0, want_samples=True):
     """sdeng_langevin_moves: ``n_moves`` MALA / ULA moves of all chains in one launch (include/sdeng.h).  ``x`` [B,d], ``lp`` [B], ``grad``

@@ -9,12 +9,15 @@ from functools import partial
 
 import torch
 
+from ..additions.ks import compute_sliced_ks
+from ..additions.mmd import mmd_median
 from ..distr.checkerboard import Checkerboard
 from ..distr.gauss import BracketTwoModes, ManyModes, TwoModes, TwoModesFull
 from ..distr.logistic_regression import LogisticRegression
 from ..distr.phi_four import PhiFour
 from ..distr.rings import Rings
 from ..engine import UnsupportedByEngine
+from ..eval.sinkhorn import Sinkhorn
 from ..models.reparam import RemoveReferenceCtrl
 from ..solver import oc
 from ..utils.common import get_timesteps
@@ -201,6 +204,8 @@ def make_model(solver_type, ref_type, loss_type, integrator_type, model_type, ti
                eval_batch_size=training_details["eval_batch_size"], train_batch_size=training_details["train_batch_size"],
                train_steps=training_details.get("train_steps", 0), optim=dict(optim_details or {}), use_ema=use_ema)  # benchmark_utils.py:181-183, 215-217
     model = cls(cfg, _make_target(target_details), device=device)
+    if compute_samples_based_metrics:  # benchmark_utils.py:222-227
+        model.eval_sample_losses = {"sinkhorn": Sinkhorn(), "mmd": mmd_median, "ks": compute_sliced_ks}
     if "ref" in solver_type:
         if ref_type == "gaussian":
             model.change_reference_type(ref_type="gaussian", mean=solver_details["mean_ref"], var=solver_details["var_ref"])

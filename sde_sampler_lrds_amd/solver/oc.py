@@ -17,6 +17,7 @@ import torch
 from ..distr.delta import Delta
 from ..distr.gauss import Gauss, GaussFull, IsotropicGauss
 from ..eq import sdes
+from ..eval.metrics import get_metrics
 from ..losses import oc as losses
 from ..models.mlp import FourierMLP, TimeEmbed
 from ..models.reparam import CancelDriftCtrl, ClippedCtrl, LerpCtrl, ScoreCtrl
@@ -72,6 +73,10 @@ class TrainableDiff:
         # solver/oc.py:37 sets True for every diffusion solver and :356/:436 switch it off for PIS/DDS; here it is on
         # only where compute_eubo is a HIP launch (the reference-SDE losses of RDS)
         self.eubo_available = False
+        # solver/base.py:68-89: the sample losses get_metrics applies to (samples, target samples) -- make_model attaches Sinkhorn, MMD
+        # and the sliced KS distance -- and the coordinates whose marginal mean / stddev it reports
+        self.eval_sample_losses = None
+        self.eval_marginal_dims = list(cfg.get("eval_marginal_dims", []))
         self.seed = cfg.get("seed", 1)
         torch.manual_seed(self.seed)
         self.setup_models()
@@ -164,9 +169,26 @@ class TrainableDiff:
     def _plain_grid(self):
         return "sde" not in self.eval_timesteps.keywords
 
+    def get_metrics(self, results: Results) -> dict:
+        """The metrics half of ``get_metrics_and_plots`` (solver/base.py:115-158; no plots, no wandb, no files): ``results.metrics``
+        gains what ``eval/metrics.py:get_metrics`` computes from the samples."""
+        metrics = results.metrics
+        if results.samples is not None:
+            metrics.update(get_metrics(distr=self.target, samples=results.samples, weights=results.weights,
+                                       log_norm_const_preds=results.log_norm_const_preds, expectation_preds=results.expectation_preds,
+                                       marginal_dims=self.eval_marginal_dims, sample_losses=self.eval_sample_losses))
+            if hasattr(self.target, "metrics"):
+                metrics.update(self.target.metrics(results.samples))
+        return metrics
+
     @torch.no_grad()
-    def evaluate(self, use_ema=True) -> Results:
-        return self.compute_results(use_ema=use_ema)
+    def evaluate(self, use_ema=True, log=False) -> Results:
+        """``log=True`` merges the sample metrics into ``results.metrics`` as upstream's ``log()`` does after every evaluation
+        (solver/base.py:160-180); off by default, so a plain ``evaluate()`` costs and returns what it always did."""
+        results = self.compute_results(use_ema=use_ema)
+        if log:
+            self.get_metrics(results)
+        return results
 
     def state_dict(self):
         return {"generative_ctrl": self.generative_ctrl.state_dict(), "loss": self.loss.state_dict()}

@@ -1,0 +1,217 @@
+"""Sample-quality metrics, the parts that need no GPU: the C ABI's declarations, the host-side metrics (mode weights, sliced KS,
+get_metrics) on CPU tensors against fixtures made by the reference (tests/golden/gen_golden_metrics.py), and the argument checks."""
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from sde_sampler_lrds_amd import _lib
+from sde_sampler_lrds_amd.additions.ks import compute_sliced_ks
+from sde_sampler_lrds_amd.additions.mmd import mmd_median
+from sde_sampler_lrds_amd.distr import base as dbase
+from sde_sampler_lrds_amd.distr.checkerboard import Checkerboard
+from sde_sampler_lrds_amd.distr.gauss import GMM, BracketTwoModes, Gauss, GMMFull, IsotropicGauss, ManyModes, TwoModes, TwoModesFull
+from sde_sampler_lrds_amd.distr.logistic_regression import LogisticRegression
+from sde_sampler_lrds_amd.distr.phi_four import PhiFour
+from sde_sampler_lrds_amd.distr.rings import Rings
+from sde_sampler_lrds_amd.eval.metrics import abs_and_rel_error, compute_errors, frac_inside_domain, get_metrics
+from sde_sampler_lrds_amd.eval.sinkhorn import Sinkhorn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+SUMMARY = json.load(open(os.path.join(GOLDEN, "metrics_summary.json")))
+HOST = np.load(os.path.join(GOLDEN, "metrics_host.npz"))
+NEW_EXPORTS = ("sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes")
+FIVE = ("compute_mode_count", "entropy", "kl_weights", "tv_weights", "compute_forgotten_modes")
+
+
+def test_exports_declared_and_abi_unchanged():
+    header = open(os.path.join(ROOT, "include", "sdeng.h")).read()
+    for name in NEW_EXPORTS:
+        assert name in _lib.EXPORTS
+        assert re.search(r"\b" + name + r"\(", header), name
+    assert _lib.ABI_VERSION == 4
+    assert re.search(r"#define SDENG_ABI_VERSION 4\b", header)
+
+
+def test_metric_unit_is_built():
+    from sde_sampler_lrds_amd import build
+    assert any(os.path.basename(s) == "metric_kernels.hip" for s in build.sources())
+
+
+def _targets():
+    return {"many_modes": ManyModes(n_modes=8, dim=2), "rings": Rings(), "checkerboard": Checkerboard()}
+
+
+@pytest.mark.parametrize("name", ["many_modes", "rings", "checkerboard"])
+def test_mode_weight_metrics_match_reference(name):
+    tgt, ref = _targets()[name], SUMMARY["host"][name]
+    smp = torch.from_numpy(HOST[f"{name}_samples"])
+    counts = tgt.compute_mode_count(smp)
+    assert list(counts.shape) == ref["counts_shape"]
+    assert torch.equal(counts, torch.from_numpy(HOST[f"{name}_counts"]))  # exactly
+    got = {"emc": tgt.entropy(smp), "kl_weights": tgt.kl_weights(smp), "tv_weights": tgt.tv_weights(smp),
+           "num_forgotten_modes": tgt.compute_forgotten_modes(smp)}
+    for key, val in got.items():
+        assert val.item() == pytest.approx(ref[key], rel=1e-5, abs=1e-7), key
+    # the counts may be handed in, as the reference's compute_stats does
+    assert tgt.entropy(smp, counts=counts).item() == got["emc"].item()
+
+
+def test_has_entropy_is_truthful():
+    gauss2 = torch.ones(1, 2)
+    objs = [ManyModes(n_modes=3, dim=2), TwoModes(dim=2), BracketTwoModes(dim=2), TwoModesFull(dim=2), Rings(), Checkerboard(),
+            Gauss(dim=2), IsotropicGauss(dim=2), GMM(dim=2, loc=gauss2, scale=gauss2), PhiFour(a=0.1, b=0.0, dim=8),
+            LogisticRegression(X_train=torch.rand(10, 3), y_train=torch.ones(10))]
+    for obj in objs:
+        has_all = all(callable(getattr(obj, m, None)) for m in FIVE)
+        if obj.has_entropy():
+            assert has_all, type(obj).__name__
+    assert [o.has_entropy() for o in objs] == [True] * 6 + [False] * 5
+    assert dbase.Distribution(dim=2).has_entropy() is False
+
+
+def test_two_mode_weight_and_phi_four_weight():
+    for cls in (TwoModes, BracketTwoModes, TwoModesFull):
+        tgt = cls(dim=2)
+        smp = torch.cat([tgt.loc[0].expand(30, -1), tgt.loc[1].expand(10, -1)]) + 0.01
+        assert tgt.compute_mode_weight(smp).item() == pytest.approx(75.0)
+        assert torch.equal(tgt.compute_mode_count(smp), torch.tensor([30.0, 10.0]))
+    phi = PhiFour(a=0.1, b=0.0, dim=8)
+    smp = torch.ones(10, 8)
+    smp[:4] *= -1
+    assert phi.compute_phi_four_weight(smp).item() == pytest.approx(4 / 6)
+
+
+def test_predictive_log_prob_only_with_a_test_split():
+    X, y = torch.rand(12, 3), (torch.rand(12) > 0.5).float()
+    plain = LogisticRegression(X_train=X, y_train=y)
+    assert not hasattr(plain, "compute_predictive_log_prob")
+    full = LogisticRegression(X_train=X, y_train=y, X_test=X[:5], y_test=y[:5])
+    w = torch.randn(7, 4)
+    same = LogisticRegression(X_train=X[:5], y_train=y[:5])  # the predictive log-density is the posterior on the test split
+    assert full.compute_predictive_log_prob(w).item() == pytest.approx(same.unnorm_log_prob(w).mean().item(), rel=1e-6)
+    assert "eval/avg_predictive_log_prob" in get_metrics(full, w) and "eval/avg_predictive_log_prob" not in get_metrics(plain, w)
+
+
+def test_sliced_ks_matches_reference():
+    s1, s2 = torch.from_numpy(HOST["ks_samples1"]), torch.from_numpy(HOST["ks_samples2"])
+    w, projs = torch.from_numpy(HOST["ks_weights"]), torch.from_numpy(HOST["ks_projs"])
+    ref = SUMMARY["host"]["ks"]
+    tol = 2.0 / s1.shape[0]  # two samples per projection may land in the neighbouring bin (the bin index is a floating-point quotient)
+    got, got_w = compute_sliced_ks(s1, s2, random_projs=projs).item(), compute_sliced_ks(s1, s2, weights=w, random_projs=projs).item()
+    print(f"sliced KS {got:.6f} (reference {ref['value']:.6f}), weighted {got_w:.6f} (reference {ref['value_weighted']:.6f})")
+    assert abs(got - ref["value"]) <= tol
+    assert abs(got_w - ref["value_weighted"]) <= tol
+    # same seed, same projections: drawn from torch's global generator on the CPU as the reference does
+    torch.manual_seed(ref["seed"])
+    assert compute_sliced_ks(s1, s2).item() == got
+    assert compute_sliced_ks(s1, s1, random_projs=projs).item() == 0.0
+
+
+def test_sliced_ks_histogram_semantics():
+    """Bins over samples1's [min, max], last bin closed on the right, samples2 outside that range dropped, own normalisation."""
+    proj = torch.tensor([[1.0]])
+    s1 = torch.tensor([[0.0], [1.0], [2.0], [4.0]])   # bins [0,1) [1,2) [2,3) [3,4]: cdf 1/4 2/4 3/4 1
+    s2 = torch.tensor([[-1.0], [0.5], [4.0], [9.0]])  # -1 and 9 dropped: cdf 1/2 1/2 1/2 1
+    assert compute_sliced_ks(s1, s2, n_bins=4, random_projs=proj).item() == pytest.approx(0.25)
+
+
+def test_get_metrics_matches_reference():
+    tgt = TwoModes(dim=2)
+    tgt.expectations = {"square": 2.1, "mode_weight": 66.0}
+    smp, wts = torch.from_numpy(HOST["get_metrics_samples"]), torch.from_numpy(HOST["get_metrics_weights"])
+    got = get_metrics(tgt, smp, weights=wts, log_norm_const_preds={"log_norm_const_is": 0.07}, expectation_preds={"square": 2.3},
+                      marginal_dims=[0, 1, 5], sample_losses=None)
+    ref = SUMMARY["host"]["get_metrics"]
+    assert set(got) == set(ref)
+    for key, val in ref.items():
+        assert got[key] == pytest.approx(val, rel=1e-6, abs=1e-9), key
+
+
+def test_get_metrics_sample_losses_and_helpers():
+    tgt = TwoModes(dim=2)
+    smp = tgt.sample((64,))
+    seen = {}
+
+    def loss(a, b):
+        seen["shapes"] = (a.shape, b.shape)
+        return (a.mean() - b.mean()).abs()
+
+    out = get_metrics(tgt, smp, marginal_dims=[], sample_losses={"toy": loss})
+    assert "error/toy" in out and "eval/frac_groundtruth_in_domain" in out and seen["shapes"] == (smp.shape, smp.shape)
+    assert abs_and_rel_error(1.5, 1.0, suffix="/x") == {"error/x": 0.5, "rel_error/x": pytest.approx(0.5)}
+    assert compute_errors(torch.tensor([[1.0], [3.0]]), target=1.0, name="q", weights=torch.tensor([[1.0], [0.0]])) == {
+        "eval/q": 2.0, "eval/q_is": 1.0, "error/q": 1.0, "rel_error/q": pytest.approx(1.0), "error/q_is": 0.0, "rel_error/q_is": 0.0}
+    assert frac_inside_domain(torch.tensor([[0.0, 0.0], [2.0, 0.0]]), torch.tensor([[-1.0, 1.0], [-1.0, 1.0]])) == 0.5
+
+
+def test_sinkhorn_argument_errors_as_upstream():
+    with pytest.raises(TypeError):
+        Sinkhorn(p=2.0)
+    with pytest.raises(ValueError):
+        Sinkhorn(p=0)
+    with pytest.raises(ValueError):
+        Sinkhorn(eps=0.0)
+    with pytest.raises(TypeError):
+        Sinkhorn(max_iters=0)
+    with pytest.raises(TypeError):
+        Sinkhorn(max_iters=10.0)
+    with pytest.raises(TypeError):
+        Sinkhorn(stop_thresh=1)
+    s = Sinkhorn()
+    assert (s.p, s.eps, s.max_iters, s.stop_thresh, s.verbose, s.n_max) == (2, 1e-3, 100, 1e-5, False, None)
+    x, y = torch.zeros(4, 2), torch.zeros(5, 2)
+    for bad in ((x[0], y), (x, y[0]), (x, torch.zeros(5, 3))):
+        with pytest.raises(ValueError):
+            s.compute(*bad)
+    w4, w5 = torch.ones(4) / 4, torch.ones(5) / 5
+    with pytest.raises(ValueError):
+        s.compute(x, y, w_x=w4)
+    with pytest.raises(ValueError):
+        s.compute(x, y, w_y=w5)
+    with pytest.raises(ValueError):
+        s.compute(x, y, w_x=w5, w_y=w5)
+    with pytest.raises(ValueError):
+        s.compute(x, y, w_x=torch.ones(2, 2), w_y=w5)
+
+
+def test_kernels_have_no_cpu_path():
+    x, y = torch.randn(8, 2), torch.randn(8, 2)
+    with pytest.raises(RuntimeError, match="MI355X"):
+        Sinkhorn()(x, y)
+    with pytest.raises(RuntimeError, match="MI355X"):
+        mmd_median(x, y)
+    with pytest.raises(AssertionError):
+        mmd_median(x, y[:4])
+
+
+def test_summary_is_consistent_with_the_fixtures():
+    """F is the largest relative |ref32 - ref64| of the stored cases; the early-stopping case stops early; MMD cases are not clamped."""
+    for metric in ("sinkhorn", "mmd"):
+        rels = {}
+        for name in SUMMARY[metric]["rel_ref32_vs_ref64"]:
+            c = np.load(os.path.join(GOLDEN, f"metrics_{name}.npz"))
+            r64, r32 = float(c[f"{metric}_ref64"]), float(c[f"{metric}_ref32"])
+            rels[name] = abs(r32 - r64) / r64
+            if metric == "mmd":
+                assert r64 > 1e-3
+        assert max(rels.values()) == pytest.approx(SUMMARY[metric]["F"], rel=1e-9)
+    c = np.load(os.path.join(GOLDEN, "metrics_d2_eps_large.npz"))
+    assert int(c["sinkhorn_iters64"]) < 100
+
+
+def test_make_model_attaches_the_sample_losses():
+    from sde_sampler_lrds_amd.experiments.benchmark_utils import make_model, make_target_details
+    args = ("vp-ref", "default", "lv", "ei", "base_zero_init", "uniform", dict(sigma=1.0), make_target_details("many_modes", dim=2, n_modes=4),
+            dict(train_steps=1, train_batch_size=64, eval_batch_size=256))
+    model = make_model(*args, n_steps=8, device="cpu")
+    assert list(model.eval_sample_losses) == ["sinkhorn", "mmd", "ks"]
+    assert isinstance(model.eval_sample_losses["sinkhorn"], Sinkhorn) and model.eval_sample_losses["mmd"] is mmd_median
+    assert model.eval_sample_losses["ks"] is compute_sliced_ks and model.eval_marginal_dims == []
+    assert make_model(*args, n_steps=8, device="cpu", compute_samples_based_metrics=False).eval_sample_losses is None
+    import inspect
+    assert inspect.signature(model.evaluate).parameters["log"].default is False
