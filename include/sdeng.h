@@ -347,6 +347,44 @@ typedef struct sdeng_adjoint {
 int sdeng_kl_adjoint(const sdeng_desc* desc, const sdeng_adjoint* adj, void* stream);
 size_t sdeng_kl_adjoint_workspace_bytes(const sdeng_desc* desc);
 
+/* KL-method training of CMCD (ControlledLangevinSDELoss with method 'kl' / 'kl_ito': back-propagation through simulate(train=True),
+ * losses/oc.py:666-755, rnd0 = 0 :695-699, with the annealed drift of eq/sdes.py:101-110 whose clip is per element, utils/common.py:109-112)
+ * as ONE launch.  Step j of that loop reads the control and the drift at BOTH of its ends,
+ *     x_{j+1} = x_j + (b_j + g u_j) dt_j + g db_j ;   cost_j = (b_j + b_{j+1})/g + u_j - u_{j+1} ;   rnd += 0.5 |cost_j|^2 dt_j + <cost_j, db_j>
+ * (:722-742; u_j = ctrl(t_j, x_j) at FORWARD time, b_j = clip(0.5 g^2 (tau_j s_pi(x_j) + (1 - tau_j) s_prior(x_j)), +-cmcd_clip), tau_j = t_j/T,
+ * db_j = sqrt(dt_j) z_j), so evaluation point j = 0 .. N receives cotangents from steps j - 1 and j.  The states xs[j] (sdeng_simulate's
+ * xs_out, all N + 1 of them) are constants; the caller evaluates the costs in one batched forward pass and passes
+ *     cbar[j] = cost_j dt_j + db_j          (0 <= j < N; per unit weight)
+ * and per 16 particles the kernel walks j = N .. 0 with the adjoint state Lambda in registers (c_j = w_b cbar[j], c_{-1} = c_N = 0, dt_N = 0):
+ *     ubar_j   = g dt_j Lambda + c_j - c_{j-1}                     cotangent of u_j
+ *     v_j      = dt_j Lambda + (c_j + c_{j-1}) / g                 cotangent of b_j
+ *     Lambda  += J_u(t_j, xs[j])^T ubar_j + 0.5 g^2 (tau_j H_pi(xs[j]) + (1 - tau_j) H_prior) (mask_j * v_j)
+ * starting from lam_in = d (sum_b w_b (-log pi~(x_N,b))) / d x_N.  mask_j = 1 where the unclipped drift lies in [-cmcd_clip, cmcd_clip] (torch.clip's
+ * backward); H_prior = -1/var on the diagonal; H_pi = the closed-form Hessian-vector product of a diagonal mixture / Gaussian or of the phi^4
+ * lattice.  For a target whose score the reference makes by autograd WITHOUT a graph (distr/base.py:146-154: LogisticRegression) backward()
+ * sees the score as a constant of x: the caller passes the target score of every row in `score` (sdeng_dist_eval), it feeds the drift's clip
+ * mask and a ScoreCtrl's score term, and H_pi = 0.  J_u^T and the per-row outputs are those of sdeng_kl_adjoint over the (N + 1) * B rows
+ * (row = j * B + b): ClippedCtrl, or ScoreCtrl (models/reparam.py:63-117: + scale s_theta(t_j) H_pi under the score clip's mask unless
+ * detach_score, and `dst`).  A particle with w_b = 0 (filtered by the loss) contributes exactly zero, whatever its costs hold.
+ * Reads desc->{abi_version, B, d, N (steps), coef ([N + 1][SDENG_NCOEF], the SDENG_FORM_CMCD table sdeng_simulate was given), net, target, prior,
+ * cmcd_g, cmcd_clip, workspace}.  SDENG_E_UNSUPPORTED, each with its reason in sdeng_last_error(): a full-covariance prior (GAUSS_FULL), a
+ * full-covariance target (GAUSS_FULL / GMM_FULL), a RINGS target, a CHECKERBOARD target, d > 128, a control other than ClippedCtrl / ScoreCtrl
+ * (KL training of those runs the adjoint step by step on the host). */
+typedef struct sdeng_cmcd_adjoint {
+  const float* xs;      /* [N+1][B][d] states x_0 .. x_N                                                      */
+  const float* cbar;    /* [N][B][d] cost_j dt_j + db_j                                                        */
+  const float* w;       /* [B] d loss / d rnd_b                                                                */
+  const float* lam_in;  /* [B][d]                                                                              */
+  float* lam_out;       /* [B][d] Lambda_0, or NULL                                                            */
+  float *a0, *a1, *a2, *d0, *d1, *d2; /* [(N+1)*B][64] each, as sdeng_ctrl_vjp                                 */
+  float* dout;          /* [(N+1)*B][d]                                                                        */
+  float* dst;           /* [(N+1)*B] ScoreCtrl: <ubar, scale clip(score_pi)>, the cotangent of s_theta(t_j) per particle; else NULL */
+  int32_t detach_score; /* ScoreCtrl(detach_score=True)                                                        */
+  const float* score;   /* [(N+1)*B][d]: the target score of every row; required for a LOGREG target (graph-less score), else NULL */
+} sdeng_cmcd_adjoint;
+int sdeng_cmcd_kl_adjoint(const sdeng_desc* desc, const sdeng_cmcd_adjoint* adj, void* stream);
+size_t sdeng_cmcd_kl_adjoint_workspace_bytes(const sdeng_desc* desc);
+
 /* Annealed samplers: n_moves Langevin moves of B chains in ONE launch -- mala_step / ula_step of additions/mcmc.py:77-135,
  * 189-221 with the per-chain step-size heuristic of :55-74 (target_acceptance > 0), as smc_sampler / re_sampler / mcmc_sample apply
  * them move after move (additions/ebm_mle.py:120-160, 340-380; experiments/benchmark_utils.py:300-330).  Density: the geometric path

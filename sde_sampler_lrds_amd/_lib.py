@@ -52,6 +52,11 @@ class Adjoint(C.Structure):  # sdeng_adjoint (include/sdeng.h)
         ("detach_score", C.c_int32), ("score", C.c_void_p)]
 
 
+class CmcdAdjoint(C.Structure):  # sdeng_cmcd_adjoint (include/sdeng.h)
+    _fields_ = [(n, C.c_void_p) for n in ("xs", "cbar", "w", "lam_in", "lam_out", "a0", "a1", "a2", "d0", "d1", "d2", "dout", "dst")] + [
+        ("detach_score", C.c_int32), ("score", C.c_void_p)]
+
+
 class Desc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("form", C.c_int32), ("flags", C.c_uint32),
                 ("B", C.c_int32), ("d", C.c_int32), ("N", C.c_int32),
@@ -80,7 +85,8 @@ EXPORTS = ["sdeng_abi_version", "sdeng_last_error", "sdeng_workspace_bytes", "sd
            "sdeng_logz_workspace_bytes", "sdeng_ctrl_forward", "sdeng_dist_eval", "sdeng_dist_workspace_bytes",
            "sdeng_philox_normal", "sdeng_philox_normal_steps", "sdeng_sample_x0", "sdeng_ctrl_vjp", "sdeng_ctrl_vjp_workspace_bytes",
            "sdeng_langevin_moves", "sdeng_langevin_moves_workspace_bytes", "sdeng_kl_adjoint", "sdeng_kl_adjoint_workspace_bytes",
-           "sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes"]
+           "sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes",
+           "sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes"]
 
 
 def lib() -> C.CDLL:
@@ -121,6 +127,10 @@ def lib() -> C.CDLL:
     L.sdeng_kl_adjoint.argtypes = [C.POINTER(Desc), C.POINTER(Adjoint), C.c_void_p]
     L.sdeng_kl_adjoint_workspace_bytes.restype = C.c_size_t
     L.sdeng_kl_adjoint_workspace_bytes.argtypes = [C.POINTER(Desc)]
+    L.sdeng_cmcd_kl_adjoint.restype = C.c_int
+    L.sdeng_cmcd_kl_adjoint.argtypes = [C.POINTER(Desc), C.POINTER(CmcdAdjoint), C.c_void_p]
+    L.sdeng_cmcd_kl_adjoint_workspace_bytes.restype = C.c_size_t
+    L.sdeng_cmcd_kl_adjoint_workspace_bytes.argtypes = [C.POINTER(Desc)]
     L.sdeng_ctrl_vjp_workspace_bytes.restype = C.c_size_t
     L.sdeng_ctrl_vjp_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     L.sdeng_langevin_moves.restype = C.c_int

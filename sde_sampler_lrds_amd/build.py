@@ -72,6 +72,9 @@ UNITS = {
     # drift-net VJP (GX: with the input gradient) and the KL adjoint (SCORE: ADJ_NONE, _GMM, _PHI4, _EXT) share a unit
     **{f"vjp_{nt}": [("vjp", nt, (gx,)) for gx in (1, 0)] + [("adj", nt, (sc,)) for sc in (0, 1, 2, 3)] for nt in DTS},
     "euler_inst": [("euler", nt, (sc,)) for nt in DTS for sc in (0, 1, 2)],  # SDEs without a drift net
+    # the CMCD KL adjoint (TGT: CADJ_GMM 1, CADJ_PHI4 2, CADJ_EXT 3 = logistic regression, d <= 64 like its step loop): one unit per
+    # instance -- each holds a whole drift-net forward + backward, and a unit of its own keeps the parallel build balanced
+    **{f"cadj_{nt}_{tgt}": [("cadj", nt, (tgt,))] for nt in DTS for tgt in (1, 2, 3) if tgt != 3 or nt <= 4},
 }
 # family -> (header, launcher template, registry enum); the enum order is the registry's sort order (sim_common.hpp)
 FAMILIES = {
@@ -82,6 +85,7 @@ FAMILIES = {
     "cmcd": ("cmcd_kernel.hpp", "launch_cmcd", "SD_FAM_CMCD"),
     "vjp": ("grad_kernel.hpp", "launch_ctrl_vjp", "SD_FAM_VJP"),
     "adj": ("grad_kernel.hpp", "launch_kl_adjoint", "SD_FAM_ADJ"),
+    "cadj": ("cmcd_adjoint_kernel.hpp", "launch_cmcd_kl_adjoint", "SD_FAM_CADJ"),
 }
 
 

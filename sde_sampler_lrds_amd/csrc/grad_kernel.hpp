@@ -199,11 +199,11 @@ SD_INLINE void vjp_tile(const VjpArgs& a, const float* lds, const float* lds_t, 
 
 // LDS of both kernels below: forward W_in, W_1, W_2, then the transposed W_out^T, W_2^T, W_1^T (same three slots of the transposed image);
 // the forward W_out (clip mask, u) and W_in^T (state gradient only) are read through L2
-SD_INLINE void vjp_stage_weights(const VjpArgs& a, float* lds, int NF, int tid) {
+SD_INLINE void vjp_stage_weights(const VjpArgs& a, float* lds, int NF, int tid, int threads = SD_THREADS) {  // threads: the workgroup's size
   const f32x4* s0 = reinterpret_cast<const f32x4*>(a.wpack);
   const f32x4* s1 = reinterpret_cast<const f32x4*>(a.wpack_t);
   f32x4* dst = reinterpret_cast<f32x4*>(lds);
-  for (int i = tid; i < NF / 4; i += SD_THREADS) {
+  for (int i = tid; i < NF / 4; i += threads) {
     dst[i] = s0[i];
     dst[NF / 4 + i] = s1[i];
   }

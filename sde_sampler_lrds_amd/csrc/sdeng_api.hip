@@ -17,6 +17,7 @@
 #include "sim_kernel.hpp"
 #include "cmcd_kernel.hpp"
 #include "grad_kernel.hpp"
+#include "cmcd_adjoint_kernel.hpp"
 #include "metric_kernels.hpp"
 
 int sd_launch_logreg_images(const float* X, const float* y, int n, int dw, int NT, float* image, float* y_pad, hipStream_t s);
@@ -81,7 +82,7 @@ struct KernelKey {
   sd_launcher fn;
 };
 static int select_kernel(KernelKey& k, int fam, int nt, int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0) {
-  static const char* const kFamily[] = {"k_simulate", "k_ctrl_forward", "k_simulate_split", "k_euler", "k_simulate_cmcd", "k_ctrl_vjp", "k_kl_adjoint"};
+  static const char* const kFamily[] = {"k_simulate", "k_ctrl_forward", "k_simulate_split", "k_euler", "k_simulate_cmcd", "k_ctrl_vjp", "k_kl_adjoint", "k_cmcd_kl_adjoint"};
   k = KernelKey{fam, nt, {p0, p1, p2, p3}, nullptr};
   const uint32_t key = sd_key(fam, nt, p0, p1, p2, p3);
   const SdKernelEntry* end = sd_registry + sd_registry_size;
@@ -899,6 +900,109 @@ extern "C" int sdeng_kl_adjoint(const sdeng_desc* d, const sdeng_adjoint* adj, v
   v.trash = ws + A.v.trash;
   a.coef = d->coef; a.noise = ito ? adj->noise : nullptr; a.w = adj->w; a.lam_in = adj->lam_in; a.lam_out = adj->lam_out;
   a.lin = d->form == SDENG_FORM_LIN ? 1 : 0;
+  a.ntiles_b = (d->B + 15) / 16;
+  SD_HIP(k.fn(&a, s));
+  return 0;
+}
+
+// ---- KL training of CMCD: the adjoint over the N + 1 evaluation points (cmcd_adjoint_kernel.hpp k_cmcd_kl_adjoint) -------------------
+struct CmcdAdjLayout {
+  VjpLayout v;
+  size_t stheta, target, prior, total;
+};
+static CmcdAdjLayout cmcd_adjoint_layout(const sdeng_desc* d, int DT) {
+  CmcdAdjLayout A;
+  A.v = vjp_layout(DT, d->N + 1);
+  size_t o = A.v.total;
+  A.stheta = o; o += align64(static_cast<size_t>(d->N) + 1);
+  A.target = o; o += dist_floats(d->target, 16 * DT);
+  A.prior = o; o += dist_floats(d->prior, 16 * DT);
+  A.total = o;
+  return A;
+}
+static int check_cmcd_adjoint(const sdeng_desc* d, bool ext_score) {
+  if (!d) return fail(SDENG_E_INVALID, "null descriptor");
+  SD_TRY(check_abi(d));
+  if (d->d > 128) return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: d <= 128 (got %d)", d->d);
+  if (d->d < 1 || d->N < 1 || d->B < 1 || !d->coef) return fail(SDENG_E_INVALID, "bad sizes (1 <= d, N, B >= 1) or null coef");
+  if (d->net.ctrl_kind != SDENG_CTRL_CLIPPED && d->net.ctrl_kind != SDENG_CTRL_SCORE)
+    return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: ClippedCtrl or ScoreCtrl (ctrl_kind %d)", d->net.ctrl_kind);
+  if (d->prior.kind == SDENG_DIST_GAUSS_FULL)
+    return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: no adjoint for a full-covariance prior (KL training takes the per-step path)");
+  if (d->prior.kind != SDENG_DIST_ISO_GAUSS && d->prior.kind != SDENG_DIST_GAUSS_DIAG)
+    return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: prior must be ISO_GAUSS or GAUSS_DIAG (kind %d)", d->prior.kind);
+  switch (d->target.kind) {
+    case SDENG_DIST_GAUSS_FULL:
+    case SDENG_DIST_GMM_FULL:
+      return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: no adjoint for a full-covariance target (kind %d)", d->target.kind);
+    case SDENG_DIST_RINGS:
+      return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: no adjoint for a rings target (KL training takes the per-step path)");
+    case SDENG_DIST_CHECKERBOARD:
+      return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: no adjoint for a checkerboard target (KL training takes the per-step path)");
+    case SDENG_DIST_LOGREG:
+      if (!ext_score) return fail(SDENG_E_INVALID, "cmcd_kl_adjoint: a logistic-regression target needs the score of every row (adj->score)");
+      if (d->d > 64) return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: logistic regression with d <= 64 (got %d), as its step loop", d->d);
+      break;
+    case SDENG_DIST_GMM_DIAG:
+    case SDENG_DIST_GAUSS_DIAG:
+    case SDENG_DIST_PHI4:
+      if (ext_score) return fail(SDENG_E_INVALID, "cmcd_kl_adjoint: adj->score is for targets with a graph-less score (LOGREG); kind %d has a closed form", d->target.kind);
+      break;
+    default:
+      return fail(SDENG_E_UNSUPPORTED, "cmcd_kl_adjoint: target must be GMM_DIAG, GAUSS_DIAG, PHI4 or LOGREG (kind %d)", d->target.kind);
+  }
+  if ((static_cast<long long>(d->N) + 1) * d->B * d->d >= (1ll << 31)) return fail(SDENG_E_UNSUPPORTED, "(N + 1) * B * d >= 2^31");
+  SD_TRY(check_net(d->net));
+  SD_TRY(check_dist(d->prior, d->d));
+  return ext_score ? 0 : check_dist(d->target, d->d);
+}
+extern "C" size_t sdeng_cmcd_kl_adjoint_workspace_bytes(const sdeng_desc* d) {
+  if (!d || d->d < 1 || d->d > 128 || d->N < 1) return 0;
+  return cmcd_adjoint_layout(d, tiles_exact(d->d)).total * sizeof(float);
+}
+extern "C" int sdeng_cmcd_kl_adjoint(const sdeng_desc* d, const sdeng_cmcd_adjoint* adj, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SD_TRY(check_cmcd_adjoint(d, adj && adj->score));
+  if (!adj || !adj->xs || !adj->cbar || !adj->w || !adj->lam_in || !adj->a0 || !adj->a1 || !adj->a2 || !adj->d0 || !adj->d1 || !adj->d2 || !adj->dout)
+    return fail(SDENG_E_INVALID, "cmcd_kl_adjoint: null states / costs / weights / lam_in / per-row outputs");
+  const bool score = d->net.ctrl_kind == SDENG_CTRL_SCORE;
+  if (score && !adj->dst) return fail(SDENG_E_INVALID, "cmcd_kl_adjoint: a ScoreCtrl needs the dst output");
+  const int tgt = adj->score ? CADJ_EXT : (d->target.kind == SDENG_DIST_PHI4 ? CADJ_PHI4 : CADJ_GMM);
+  const int DT = tiles_exact(d->d), dpad = 16 * DT;
+  KernelKey k;
+  SD_TRY(select_kernel(k, SD_FAM_CADJ, DT, tgt));
+  const CmcdAdjLayout A = cmcd_adjoint_layout(d, DT);
+  const size_t need = A.total * sizeof(float);
+  if (!d->workspace || d->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", d->workspace_bytes, need);
+  float* ws = static_cast<float*>(d->workspace);
+  CmcdAdjArgs a;
+  memset(&a, 0, sizeof(a));
+  SD_TRY(pack_net(d, DT, ws, ws + A.v.wt, s));
+  SD_TRY(embed_times(d, d->N + 1, false, 0.0f, ws + A.v.temb, ws + A.stheta, &a.stheta, s));
+  if (tgt != CADJ_EXT) SD_TRY(build_dist(d->target, d->d, dpad, ws + A.target, a.target, s));
+  if (d->prior.kind == SDENG_DIST_GAUSS_DIAG) {
+    DistDev prior;
+    SD_TRY(build_dist(d->prior, d->d, dpad, ws + A.prior, prior, s));
+    a.prior_tab = prior.tab;
+  } else {
+    a.iso_loc = d->prior.p0; a.inv_iso_var = 1.0f / d->prior.p3;  // (as the step loop, run_cmcd)
+  }
+  a.g = d->cmcd_g; a.clip = d->cmcd_clip;
+  a.has_score = score ? 1 : 0;
+  if (score) {
+    a.scale_score = d->net.scale_score; a.clip_score = d->net.clip_score;
+    a.score_detached = adj->detach_score ? 1 : 0;
+    a.dst = adj->dst;
+  }
+  a.score_ext = adj->score;
+  VjpArgs& v = a.v;
+  v.M = (d->N + 1) * d->B; v.B = d->B; v.d = d->d; v.N = d->N + 1;
+  v.x = adj->xs; v.cot = nullptr; v.wpack = ws; v.wpack_t = ws + A.v.wt; v.temb = ws + A.v.temb;
+  v.clip_model = d->net.clip_model;
+  v.a0 = adj->a0; v.a1 = adj->a1; v.a2 = adj->a2; v.d0 = adj->d0; v.d1 = adj->d1; v.d2 = adj->d2; v.dout = adj->dout;
+  v.trash = ws + A.v.trash;
+  a.coef = d->coef; a.cbar = adj->cbar; a.w = adj->w; a.lam_in = adj->lam_in; a.lam_out = adj->lam_out;
+  a.steps = d->N;
   a.ntiles_b = (d->B + 15) / 16;
   SD_HIP(k.fn(&a, s));
   return 0;

@@ -142,9 +142,9 @@ inline int sd_launch_kernel(void (*kernel)(Formals...), int grid, int block, siz
 
 // Registry of the step-loop kernel instances (gen/registry.hip, generated by build.py from its INSTANCES list).  A key is the family,
 // the feature tiles NT and the family's own template parameters after NT, in order:
-//   SIM (REF, SC, FORM, PAR)   CTRL (SC)   SPLIT (REF, FORM, PERT)   EULER (SC)   CMCD (TGT, EUBO, PAR)   VJP (GX)   ADJ (SCORE)
-// A launcher takes the family's argument block (SimArgs, CmcdArgs, VjpArgs or AdjArgs) and launches exactly that instance.
-enum { SD_FAM_SIM = 0, SD_FAM_CTRL, SD_FAM_SPLIT, SD_FAM_EULER, SD_FAM_CMCD, SD_FAM_VJP, SD_FAM_ADJ };
+//   SIM (REF, SC, FORM, PAR)   CTRL (SC)   SPLIT (REF, FORM, PERT)   EULER (SC)   CMCD (TGT, EUBO, PAR)   VJP (GX)   ADJ (SCORE)   CADJ (TGT)
+// A launcher takes the family's argument block (SimArgs, CmcdArgs, VjpArgs, AdjArgs or CmcdAdjArgs) and launches exactly that instance.
+enum { SD_FAM_SIM = 0, SD_FAM_CTRL, SD_FAM_SPLIT, SD_FAM_EULER, SD_FAM_CMCD, SD_FAM_VJP, SD_FAM_ADJ, SD_FAM_CADJ };
 constexpr uint32_t sd_key(int fam, int nt, int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0) {  // every field < 16
   return static_cast<uint32_t>(fam) << 24 | static_cast<uint32_t>(nt) << 16 | p0 << 12 | p1 << 8 | p2 << 4 | p3;
 }

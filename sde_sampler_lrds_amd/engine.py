@@ -973,6 +973,127 @@ def kl_adjoint(ctrl, coef: torch.Tensor, xs: torch.Tensor, z, w: torch.Tensor, l
     return dict(x=x, a0=hid[0], a1=hid[1], a2=hid[2], d0=hid[3], d1=hid[4], d2=hid[5], dout=dout, gx=None, dst=dst), lam0
 
 
+def ctrl_forward_rows(ctrl, t_unique: torch.Tensor, xs: torch.Tensor) -> torch.Tensor:
+    """u = ctrl(t_k, xs[k]) for a ClippedCtrl over all rows of ``xs`` [M,B,d] in one launch (sdeng_ctrl_vjp without a cotangent): [M,B,d]."""
+    require_gpu(xs)
+    lib = L.lib()
+    device, keep = xs.device, []
+    M, B, d = xs.shape
+    desc = L.Desc()
+    desc.abi_version = L.ABI_VERSION
+    desc.net = net_desc(ctrl, device, keep)
+    if desc.net.ctrl_kind != L.CTRL_CLIPPED:
+        raise UnsupportedByEngine("ctrl_forward_rows: ClippedCtrl only")
+    desc.d = d
+    coef = torch.zeros(M, L.NCOEF, dtype=torch.float32, device=device)
+    coef[:, 0] = t_unique.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    desc.coef = coef.data_ptr()
+    x2 = xs.detach().to(torch.float32).contiguous().view(M * B, d)
+    u = torch.empty(M * B, d, dtype=torch.float32, device=device)
+    ws = _WS.get(lib.sdeng_ctrl_vjp_workspace_bytes(d, M), device)
+    desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.check(lib.sdeng_ctrl_vjp(C.byref(desc), M, B, x2.data_ptr(), None, None, None, None, None, None, None, None, None, u.data_ptr(),
+                               _stream_ptr(device)))
+    return u.view(M, B, d)
+
+
+_DIAG_TARGETS = ("GMM", "TwoModes", "ManyModes", "BracketTwoModes", "Gauss")
+
+
+def cmcd_adjoint_ok(loss) -> bool:
+    """Does sdeng_cmcd_kl_adjoint differentiate this ControlledLangevinSDELoss?  Looks at types and attributes only (no descriptor, no
+    read-back): a ClippedCtrl or plain ScoreCtrl over a FourierMLP; an IsotropicGauss or diagonal Gauss prior; a diagonal mixture /
+    Gaussian, untilted 1-D Dirichlet-0 phi^4 or logistic-regression (d <= 64) target, d <= 128 -- and the ScoreCtrl's target is the SDE's.
+    Rings, checkerboard and full-covariance priors / targets keep the per-step adjoint."""
+    ctrl, sde = loss.generative_ctrl, loss.sde
+    if _name(ctrl) not in ("ClippedCtrl", "ScoreCtrl") or _name(getattr(ctrl, "base_model", None)) != "FourierMLP":
+        return False
+    if not getattr(loss, "use_rescaling", True):
+        return False
+    target, prior = _self_of(getattr(sde, "target_score", None)), _self_of(getattr(sde, "prior_score", None))
+    if target is None or prior is None:
+        return False
+    if _name(prior) == "Gauss":
+        if getattr(prior, "mixture_weights", None) is not None or getattr(prior, "scale", None) is None:
+            return False
+    elif _name(prior) != "IsotropicGauss":
+        return False
+    dim = int(getattr(target, "dim", 0) or 0)
+    if dim < 1 or dim > 128:
+        return False
+    n = _name(target)
+    if n == "PhiFour":
+        if getattr(target, "dim_phys", 1) != 1 or tuple(getattr(target, "bc", ("dirichlet", 0))) != ("dirichlet", 0) or getattr(target, "tilt", None):
+            return False
+    elif n in _GRAPHLESS_SCORE:
+        if dim > 64:
+            return False
+    elif n not in _DIAG_TARGETS:
+        return False
+    if _name(ctrl) == "ScoreCtrl":
+        if _self_of(ctrl.target_score) is not target:
+            return False
+        return ctrl.score_model is None or _name(ctrl.score_model) == "TimeEmbed"
+    return True
+
+
+def cmcd_kl_adjoint(ctrl, sde, coef: torch.Tensor, xs: torch.Tensor, cbar: torch.Tensor, w: torch.Tensor, lam_n: torch.Tensor, score_ext=None):
+    """sdeng_cmcd_kl_adjoint: the adjoint of CMCD's KL training over the N + 1 evaluation points in one launch.  ``coef`` [N+1,16] the CMCD
+    table of the step loop (device), ``xs`` [N+1,B,d] = x_0 .. x_N, ``cbar`` [N,B,d] = cost_j dt_j + db_j, ``w`` [B,1] = d loss / d rnd,
+    ``lam_n`` [B,d] = d (sum w (-log pi~(x_N))) / d x_N.  ``score_ext`` [(N+1)*B,d]: the target score of every row for a graph-less target
+    (evaluated here when not given).  Returns (per-row arrays as ``kl_adjoint`` over the (N+1)*B rows, Lambda_0)."""
+    require_gpu(xs)
+    if xs.dim() != 3 or cbar.dim() != 3:
+        raise ValueError(f"cmcd_kl_adjoint: xs [N+1,B,d] and cbar [N,B,d] expected, got {tuple(xs.shape)} and {tuple(cbar.shape)}")
+    M, B, d = xs.shape
+    N = M - 1
+    if N < 1 or tuple(cbar.shape) != (N, B, d) or w.numel() != B or tuple(lam_n.shape) != (B, d) or tuple(coef.shape) != (M, L.NCOEF):
+        raise ValueError(f"cmcd_kl_adjoint: shapes disagree: xs {tuple(xs.shape)}, cbar {tuple(cbar.shape)} (want {(N, B, d)}), w {tuple(w.shape)} "
+                         f"(want {B} entries), lam_n {tuple(lam_n.shape)} (want {(B, d)}), coef {tuple(coef.shape)} (want {(M, L.NCOEF)})")
+    lib = L.lib()
+    device, keep = xs.device, []
+    desc = L.Desc()
+    desc.abi_version = L.ABI_VERSION
+    desc.form = L.FORM_CMCD
+    desc.B, desc.d, desc.N = B, d, N
+    desc.net = net_desc(ctrl, device, keep)
+    target, prior = _self_of(sde.target_score), _self_of(sde.prior_score)
+    if target is None or prior is None:
+        raise UnsupportedByEngine("ControlledLangevinSDE.target_score / prior_score must be bound Distribution.score methods")
+    desc.target = dist_desc(target, device, keep)
+    desc.prior = dist_desc(prior, device, keep)
+    desc.cmcd_g = scalar_of(sde.diff_coeff)
+    desc.cmcd_clip = scalar_of(sde.clip_score) if sde.clip_score else 0.0
+    x = xs.detach().to(torch.float32).contiguous().view(M * B, d)
+    if _name(target) in _GRAPHLESS_SCORE and score_ext is None:
+        _, score_ext = dist_eval(target, x, want_logp=False, want_score=True)
+    if score_ext is not None:
+        score_ext = score_ext.detach().to(torch.float32).contiguous()
+        if tuple(score_ext.shape) != (M * B, d):
+            raise ValueError(f"cmcd_kl_adjoint: score_ext {tuple(score_ext.shape)}, want {(M * B, d)}")
+    cf = coef.detach().to(device=device, dtype=torch.float32).contiguous()
+    desc.coef = cf.data_ptr()
+    cb = cbar.detach().to(torch.float32).contiguous()
+    hid = torch.empty(6, M * B, 64, dtype=torch.float32, device=device)
+    dout = torch.empty(M * B, d, dtype=torch.float32, device=device)
+    lam0 = torch.empty(B, d, dtype=torch.float32, device=device)
+    wv = w.detach().to(torch.float32).contiguous().view(B)
+    ln = lam_n.detach().to(torch.float32).contiguous()
+    ws = _WS.get(lib.sdeng_cmcd_kl_adjoint_workspace_bytes(C.byref(desc)), device)
+    desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
+    adj = L.CmcdAdjoint()
+    adj.xs, adj.cbar, adj.w, adj.lam_in, adj.lam_out = x.data_ptr(), cb.data_ptr(), wv.data_ptr(), ln.data_ptr(), lam0.data_ptr()
+    adj.a0, adj.a1, adj.a2, adj.d0, adj.d1, adj.d2 = (hid[i].data_ptr() for i in range(6))
+    adj.dout = dout.data_ptr()
+    score = desc.net.ctrl_kind != L.CTRL_CLIPPED
+    dst = torch.empty(M, B, dtype=torch.float32, device=device) if score else None
+    if score:
+        adj.dst, adj.detach_score = dst.data_ptr(), int(bool(ctrl.detach_score))
+    adj.score = score_ext.data_ptr() if score_ext is not None else None
+    L.check(lib.sdeng_cmcd_kl_adjoint(C.byref(desc), C.byref(adj), _stream_ptr(device)))
+    return dict(x=x, a0=hid[0], a1=hid[1], a2=hid[2], d0=hid[3], d1=hid[4], d2=hid[5], dout=dout, gx=None, dst=dst), lam0
+
+
 def ctrl_forward(ctrl, t: float, x: torch.Tensor, score_gain=1.0, lerp_w=0.0):
     """sdeng_ctrl_forward: u = ctrl(t, x) for a ClippedCtrl / ScoreCtrl / LerpCtrl module, computed in HIP."""
     require_gpu(x)

@@ -197,7 +197,8 @@ class BaseOCLoss:
         self._cpu_sde = None
         self.timing_events = None  # optional _lib.HipEvents: times the step-loop kernel alone
         self.graph_adjoint = True  # KL training where the adjoint runs step by step in torch (CMCD; controls / targets / references the adjoint kernel does not cover): each step replayed as a hipGraph; False: eager
-        self.native_adjoint = True  # KL training of a ClippedCtrl with no / a diagonal reference: the adjoint recursion as ONE launch (sdeng_kl_adjoint); False: one sdeng_ctrl_vjp per step
+        self.native_adjoint = True  # KL training of a ClippedCtrl with no / a diagonal reference: the adjoint recursion as ONE launch (sdeng_kl_adjoint; CMCD: sdeng_cmcd_kl_adjoint); False: one sdeng_ctrl_vjp per step (CMCD: one torch VJP per step)
+        self.last_adjoint_path = None  # CMCD KL training: 'native' | 'stepwise', which adjoint the last call ran
         self.fused_training = True  # ClippedCtrl over a FourierMLP: the batched control pass of training as ONE fused HIP forward + backward (sdeng_ctrl_vjp); False: the eager torch pass
         self.graph_training = False  # True: the batched control pass of log-variance training (forward + backward) is replayed as a hipGraph (_IntegralPass)
         self._graphed = {}
@@ -818,17 +819,8 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         with torch.no_grad():
             x_n, _, xs = self.simulate(ts, x, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False,
                                        return_traj=True, use_ema=False, noise=z)
-            flat = xs.reshape((N + 1) * B, d)
-            _, s_tgt = E.dist_eval(target, flat, want_logp=False)
-            _, s_pri = E.dist_eval(prior, flat, want_logp=False)
-            s_tgt, s_pri = s_tgt.view(N + 1, B, d), s_pri.view(N + 1, B, d)
-
-            def drift(k_time, k_state):  # eq/sdes.py:101-110 at (ts[k_time], xs[k_state])
-                w = (ts[k_time] / T).view(-1, 1, 1)
-                out = (s_tgt[k_state] * w + s_pri[k_state] * (1.0 - w)) * (0.5 * g ** 2)
-                return out if not self.sde.clip_score else out.clip(-float(self.sde.clip_score), float(self.sde.clip_score))
-            idx = torch.arange(N, device=x.device)
-            b_s, b_t = drift(idx, idx), drift(idx + 1, idx + 1)
+            b_all, _ = self._cmcd_drifts(self._coef(ts, x.device), xs)  # eq/sdes.py:101-110 at every (ts[j], xs[j])
+            b_s, b_t = b_all[:-1], b_all[1:]
             const = -terminal_unnorm_log_prob(x_n)
             if initial_log_prob is not None:
                 const = const + initial_log_prob(x).view((-1, 1))
@@ -840,6 +832,43 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
                + (cost * db).sum(-1)).sum(0).view(B, 1) + const
         return self.compute_loss(rnd, samples=x_n)
 
+
+    def _cmcd_drifts(self, coef, xs):
+        """The annealed drift b_j = clip(0.5 g^2 (tau_j s_pi(x_j) + (1 - tau_j) s_prior(x_j))) (eq/sdes.py:101-110) at all N + 1 evaluation points
+        of the HIP states ``xs`` [N+1,B,d], without a graph: target and prior scores of all rows from the distribution kernels, the annealing
+        weights tau_j = ts[j]/T from the step loop's own table ``coef`` (columns 4-7).  -> (b [N+1,B,d], target scores [(N+1)*B, d]).  Shared by
+        log-variance training and by the cost pass of the KL adjoint."""
+        M, B, d = xs.shape
+        N = M - 1
+        target = getattr(self.sde.target_score, "__self__", None)
+        prior = getattr(self.sde.prior_score, "__self__", None)
+        flat = xs.reshape(M * B, d)
+        _, s_tgt = E.dist_eval(target, flat, want_logp=False)
+        _, s_pri = E.dist_eval(prior, flat, want_logp=False)
+        g = float(self.sde.diff_coeff)
+        tau = torch.cat([coef[:N, 4], coef[N - 1:N, 6]]).view(M, 1, 1)
+        omt = torch.cat([coef[:N, 5], coef[N - 1:N, 7]]).view(M, 1, 1)
+        b = (s_tgt.view(M, B, d) * tau + s_pri.view(M, B, d) * omt) * (0.5 * g ** 2)
+        if self.sde.clip_score:
+            b = b.clip(-float(self.sde.clip_score), float(self.sde.clip_score))
+        return b, s_tgt
+
+    def _cmcd_step_costs(self, ctrl, coef, xs, z):
+        """cost_j dt_j + db_j [N,B,d] of the CMCD steps on the HIP states ``xs`` [N+1,B,d] (losses/oc.py:722-742), without a graph: the drifts
+        of ``_cmcd_drifts``, the drift net from one forward launch, the rest elementwise.  Also returns the target scores [(N+1)*B, d]."""
+        from ..models.reparam import _clip
+        M, B, d = xs.shape
+        N = M - 1
+        g = float(self.sde.diff_coeff)
+        b, s_tgt = self._cmcd_drifts(coef, xs)
+        u = E.ctrl_forward_rows(fused_net_view(ctrl), coef[:, 0], xs)
+        if type(ctrl).__name__ == "ScoreCtrl":
+            sc = ctrl.scale_score * _clip(s_tgt, ctrl.clip_score).view(M, B, d)
+            if ctrl.score_model is not None:
+                sc = sc * ctrl.clipped_score_model(coef[:, 0].contiguous().view(-1, 1), None).view(M, 1, 1)
+            u = u + sc
+        cost = (b[:-1] + b[1:]) / g + u[:-1] - u[1:]
+        return cost * coef[:N, 2].view(N, 1, 1) + coef[:N, 3].view(N, 1, 1) * z, s_tgt
 
     def _kl_loss_cmcd(self, ts, x, terminal_unnorm_log_prob, initial_log_prob):
         """[TRAINING] KL methods of CMCD (losses/oc.py:830-857 on simulate(train=True): rnd0 = 0, :695-699; the un-detached control drives
@@ -871,6 +900,39 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         grads = [torch.zeros_like(p) for p in params]
         g = self.sde.diff_coeff
         tdev = ts.to(x.device)
+        def terminal_cotangent():
+            """d (sum_b w_b (-log pi~(x_N,b))) / d x_N.  A piecewise-constant density (the checkerboard) builds no graph to x_N: its terminal
+            term contributes nothing to the reference's backward() either."""
+            with torch.enable_grad():
+                xN = x_n.detach().requires_grad_(True)
+                out = (w * (-terminal_unnorm_log_prob(xN).view(B, 1))).sum()
+                return torch.autograd.grad(out, xN)[0] if out.requires_grad else torch.zeros_like(xN)
+
+        if self.native_adjoint and E.cmcd_adjoint_ok(self):
+            # ClippedCtrl / ScoreCtrl, diagonal or isotropic prior, mixture / phi^4 / logistic-regression target: the recursion over the
+            # N + 1 evaluation points is ONE launch (sdeng_cmcd_kl_adjoint); its input, the per-step cost cotangents, is one batched
+            # forward pass over the HIP states.  Parameter gradients from the per-row arrays, as in _kl_loss.
+            self.last_adjoint_path = "native"
+            lam = terminal_cotangent()
+            coef = self._coef(ts, x.device)
+            t_all = coef[:, 0].contiguous()
+            with torch.no_grad():
+                cbar, s_tgt = self._cmcd_step_costs(ctrl, coef, xs, z)
+            graphless = type(getattr(self.sde.target_score, "__self__", None)).__name__ in E._GRAPHLESS_SCORE
+            arrays, _ = E.cmcd_kl_adjoint(ctrl, self.sde, coef, xs, cbar, w, lam, score_ext=s_tgt if graphless else None)
+            with torch.enable_grad():
+                found = vjp_param_grads(ctrl, t_all, arrays, N + 1, B)
+                sm = getattr(ctrl, "score_model", None)
+                sm_params = [p for p in sm.parameters() if p.requires_grad] if (arrays["dst"] is not None and sm is not None) else []
+                if sm_params:
+                    st = ctrl.clipped_score_model(t_all.view(-1, 1), None).view(N + 1)
+                    sm_grads = torch.autograd.grad(st, sm_params, grad_outputs=arrays["dst"].sum(1), allow_unused=True)
+                    found.update({p: gr for p, gr in zip(sm_params, sm_grads) if gr is not None})
+            grads = [found.get(p, torch.zeros_like(p)) for p in params]
+            surrogate = sum(((p - p.detach()) * gr).sum() for p, gr in zip(params, grads))
+            return value.detach() + surrogate, {"train/n_filtered_cumulative": self.n_filtered}
+        self.last_adjoint_path = "stepwise"
+
         def step(lam_in, x_in, z_in, s, t, w_in):
             """One step of the adjoint: lambda_k and the parameter-gradient contributions of step k (accumulated into ``grads``)."""
             with torch.enable_grad():
@@ -887,9 +949,7 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
                     acc.add_(gk)
             return got[0]
 
-        with torch.enable_grad():
-            xN = x_n.detach().requires_grad_(True)
-            lam, = torch.autograd.grad((w * (-terminal_unnorm_log_prob(xN).view(B, 1))).sum(), xN)
+        lam = terminal_cotangent()
         # The ~130 small kernels of one step are launch-bound (2048 x 100: 5 ms per step of the recursion): the step is captured once per
         # (shape, control) as a hipGraph and replayed N times; a capture that fails runs the steps eagerly, and says so.
         runner = _graphed_step(self, ("cmcd", id(ctrl), B, d, str(x.device)), step, grads,
