@@ -773,6 +773,25 @@ extern "C" size_t sdeng_ctrl_vjp_workspace_bytes(int32_t d, int32_t n_times) {
   if (d < 1 || d > 128 || n_times < 1) return 0;
   return vjp_layout(tiles_exact(d), n_times).total * sizeof(float);
 }
+// The part the three training entry points share, after their own validation and kernel selection: the workspace check (no HIP call
+// before it), both weight images at the front of the workspace (`pack` = 0: the caller's are still there), the time embeddings of
+// n_times rows of coef -- and the clipped score model's at `stheta_off` when the control has one --, and the VjpArgs of rows_per_time
+// rows per time with the seven per-row outputs.  V is the head of the caller's own layout of `total` floats: nothing moves.
+struct VjpOut { float *a0, *a1, *a2, *d0, *d1, *d2, *dout; };
+static int prepare_vjp(const sdeng_desc* d, int DT, const VjpLayout& V, size_t total, bool pack, int n_times, int rows_per_time, const float* x,
+                       const VjpOut& o, size_t stheta_off, const float** stheta, VjpArgs& v, hipStream_t s) {
+  const size_t need = total * sizeof(float);
+  if (!d->workspace || d->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", d->workspace_bytes, need);
+  float* ws = static_cast<float*>(d->workspace);
+  if (pack) SD_TRY(pack_net(d, DT, ws, ws + V.wt, s));
+  SD_TRY(embed_times(d, n_times, false, 0.0f, ws + V.temb, ws + stheta_off, stheta, s));
+  v.M = n_times * rows_per_time; v.B = rows_per_time; v.d = d->d; v.N = n_times;
+  v.x = x; v.wpack = ws; v.wpack_t = ws + V.wt; v.temb = ws + V.temb;
+  v.clip_model = d->net.clip_model;
+  v.a0 = o.a0; v.a1 = o.a1; v.a2 = o.a2; v.d0 = o.d0; v.d1 = o.d1; v.d2 = o.d2; v.dout = o.dout;
+  v.trash = ws + V.trash;
+  return 0;
+}
 extern "C" int sdeng_ctrl_vjp(const sdeng_desc* d, int32_t n_times, int32_t rows_per_time, const float* x, const float* cot, float* a0,
                               float* a1, float* a2, float* d0, float* d1, float* d2, float* dout, float* gx, float* u_out, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -789,20 +808,12 @@ extern "C" int sdeng_ctrl_vjp(const sdeng_desc* d, int32_t n_times, int32_t rows
   KernelKey k;
   SD_TRY(select_kernel(k, SD_FAM_VJP, DT, gx ? 1 : 0));
   const VjpLayout V = vjp_layout(DT, n_times);
-  const size_t need = V.total * sizeof(float);
-  if (!d->workspace || d->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", d->workspace_bytes, need);
-  float* ws = static_cast<float*>(d->workspace);
-  // (a caller stepping through the times one by one packs once: the images stay valid in the workspace)
-  if (!(d->flags & SDENG_FLAG_REUSE_PACK)) SD_TRY(pack_net(d, DT, ws, ws + V.wt, s));
-  const float* no_stheta;  // (ClippedCtrl: no score model)
-  SD_TRY(embed_times(d, n_times, false, 0.0f, ws + V.temb, nullptr, &no_stheta, s));
   VjpArgs a;
   memset(&a, 0, sizeof(a));
-  a.M = static_cast<int>(M); a.B = rows_per_time; a.d = d->d; a.N = n_times;
-  a.x = x; a.cot = cot; a.wpack = ws; a.wpack_t = ws + V.wt; a.temb = ws + V.temb;
-  a.clip_model = d->net.clip_model;
-  a.a0 = a0; a.a1 = a1; a.a2 = a2; a.d0 = d0; a.d1 = d1; a.d2 = d2; a.dout = dout; a.gx = gx; a.u_out = u_out;
-  a.trash = ws + V.trash;
+  const float* no_stheta;  // (ClippedCtrl: no score model)
+  // (a caller stepping through the times one by one packs once: the images stay valid in the workspace)
+  SD_TRY(prepare_vjp(d, DT, V, V.total, !(d->flags & SDENG_FLAG_REUSE_PACK), n_times, rows_per_time, x, {a0, a1, a2, d0, d1, d2, dout}, 0, &no_stheta, a, s));
+  a.cot = cot; a.gx = gx; a.u_out = u_out;
   a.ntiles = static_cast<int>((M + 15) / 16);
   SD_HIP(k.fn(&a, s));
   return 0;
@@ -863,13 +874,11 @@ extern "C" int sdeng_kl_adjoint(const sdeng_desc* d, const sdeng_adjoint* adj, v
   KernelKey k;
   SD_TRY(select_kernel(k, SD_FAM_ADJ, DT, has_score));
   const AdjLayout A = adjoint_layout(d, DT);
-  const size_t need = A.total * sizeof(float);
-  if (!d->workspace || d->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", d->workspace_bytes, need);
-  float* ws = static_cast<float*>(d->workspace);
   AdjArgs a;
   memset(&a, 0, sizeof(a));
-  SD_TRY(pack_net(d, DT, ws, ws + A.v.wt, s));
-  SD_TRY(embed_times(d, d->N, false, 0.0f, ws + A.v.temb, ws + A.stheta, &a.stheta, s));
+  SD_TRY(prepare_vjp(d, DT, A.v, A.total, true, d->N, d->B, adj->xs, {adj->a0, adj->a1, adj->a2, adj->d0, adj->d1, adj->d2, adj->dout}, A.stheta, &a.stheta,
+                     a.v, s));
+  float* ws = static_cast<float*>(d->workspace);
   if (d->ref.kind != SDENG_REF_NONE) {  // the noised reference of every step: (mean, 1/var) tables + logit constants, as the step loop reads them
     const int K = ref_components(d);
     RefTabArgs r;
@@ -892,12 +901,6 @@ extern "C" int sdeng_kl_adjoint(const sdeng_desc* d, const sdeng_adjoint* adj, v
     a.score_detached = adj->detach_score ? 1 : 0;
     a.dst = adj->dst;
   }
-  VjpArgs& v = a.v;
-  v.M = d->N * d->B; v.B = d->B; v.d = d->d; v.N = d->N;
-  v.x = adj->xs; v.cot = nullptr; v.wpack = ws; v.wpack_t = ws + A.v.wt; v.temb = ws + A.v.temb;
-  v.clip_model = d->net.clip_model;
-  v.a0 = adj->a0; v.a1 = adj->a1; v.a2 = adj->a2; v.d0 = adj->d0; v.d1 = adj->d1; v.d2 = adj->d2; v.dout = adj->dout;
-  v.trash = ws + A.v.trash;
   a.coef = d->coef; a.noise = ito ? adj->noise : nullptr; a.w = adj->w; a.lam_in = adj->lam_in; a.lam_out = adj->lam_out;
   a.lin = d->form == SDENG_FORM_LIN ? 1 : 0;
   a.ntiles_b = (d->B + 15) / 16;
@@ -972,13 +975,11 @@ extern "C" int sdeng_cmcd_kl_adjoint(const sdeng_desc* d, const sdeng_cmcd_adjoi
   KernelKey k;
   SD_TRY(select_kernel(k, SD_FAM_CADJ, DT, tgt));
   const CmcdAdjLayout A = cmcd_adjoint_layout(d, DT);
-  const size_t need = A.total * sizeof(float);
-  if (!d->workspace || d->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", d->workspace_bytes, need);
-  float* ws = static_cast<float*>(d->workspace);
   CmcdAdjArgs a;
   memset(&a, 0, sizeof(a));
-  SD_TRY(pack_net(d, DT, ws, ws + A.v.wt, s));
-  SD_TRY(embed_times(d, d->N + 1, false, 0.0f, ws + A.v.temb, ws + A.stheta, &a.stheta, s));
+  SD_TRY(prepare_vjp(d, DT, A.v, A.total, true, d->N + 1, d->B, adj->xs, {adj->a0, adj->a1, adj->a2, adj->d0, adj->d1, adj->d2, adj->dout}, A.stheta,
+                     &a.stheta, a.v, s));
+  float* ws = static_cast<float*>(d->workspace);
   if (tgt != CADJ_EXT) SD_TRY(build_dist(d->target, d->d, dpad, ws + A.target, a.target, s));
   if (d->prior.kind == SDENG_DIST_GAUSS_DIAG) {
     DistDev prior;
@@ -995,12 +996,6 @@ extern "C" int sdeng_cmcd_kl_adjoint(const sdeng_desc* d, const sdeng_cmcd_adjoi
     a.dst = adj->dst;
   }
   a.score_ext = adj->score;
-  VjpArgs& v = a.v;
-  v.M = (d->N + 1) * d->B; v.B = d->B; v.d = d->d; v.N = d->N + 1;
-  v.x = adj->xs; v.cot = nullptr; v.wpack = ws; v.wpack_t = ws + A.v.wt; v.temb = ws + A.v.temb;
-  v.clip_model = d->net.clip_model;
-  v.a0 = adj->a0; v.a1 = adj->a1; v.a2 = adj->a2; v.d0 = adj->d0; v.d1 = adj->d1; v.d2 = adj->d2; v.dout = adj->dout;
-  v.trash = ws + A.v.trash;
   a.coef = d->coef; a.cbar = adj->cbar; a.w = adj->w; a.lam_in = adj->lam_in; a.lam_out = adj->lam_out;
   a.steps = d->N;
   a.ntiles_b = (d->B + 15) / 16;

@@ -30,6 +30,11 @@ def _name(obj):
     return type(obj).__name__
 
 
+def _f32c(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as the kernels read it: no graph, float32, contiguous (``t`` itself when it already is)."""
+    return t.detach().to(torch.float32).contiguous()
+
+
 def _dev_f32(t: torch.Tensor, device, keep: list):
     t = t.detach().to(device=device, dtype=torch.float32).contiguous()
     keep.append(t)
@@ -586,7 +591,7 @@ def run(desc: L.Desc, x: torch.Tensor, keep: list, return_traj=False, noise=None
         desc.x0_dist = x.desc(keep)
         x_out = torch.empty(B, d, dtype=torch.float32, device=device)
     else:
-        xin = x.detach().to(torch.float32).contiguous()
+        xin = _f32c(x)
         keep.append(xin)
         desc.x_in = xin.data_ptr()
         x_out = torch.empty_like(xin)
@@ -683,7 +688,7 @@ def logz_stats(rnd: torch.Tensor, want_weights=True):
     require_gpu(rnd)
     lib = L.lib()
     device = rnd.device
-    r = rnd.detach().to(torch.float32).contiguous().view(-1)
+    r = _f32c(rnd).view(-1)
     stats = torch.empty(8, dtype=torch.float32, device=device)
     w = torch.empty(r.numel(), 1, dtype=torch.float32, device=device) if want_weights else None
     ws = torch.empty(lib.sdeng_logz_workspace_bytes(), dtype=torch.uint8, device=device)
@@ -701,7 +706,7 @@ def dist_eval(dist, x: torch.Tensor, want_logp=True, want_score=True):
     lib = L.lib()
     device, keep = x.device, []
     ds = dist_desc(dist, device, keep)
-    xin = x.detach().to(torch.float32).contiguous()
+    xin = _f32c(x)
     B, d = xin.shape
     logp = torch.empty(B, 1, dtype=torch.float32, device=device) if want_logp else None
     score = torch.empty(B, d, dtype=torch.float32, device=device) if want_score else None
@@ -721,10 +726,10 @@ def sinkhorn(x: torch.Tensor, y: torch.Tensor, w_x=None, w_y=None, p=2, eps=1e-3
     require_gpu(y)
     lib = L.lib()
     device = x.device
-    xin, yin = x.detach().to(torch.float32).contiguous(), y.detach().to(device, torch.float32).contiguous()
+    xin, yin = _f32c(x), _f32c(y.to(device))
     (n, d), m = xin.shape, yin.shape[0]
-    wx = None if w_x is None else w_x.detach().to(device, torch.float32).contiguous()
-    wy = None if w_y is None else w_y.detach().to(device, torch.float32).contiguous()
+    wx = None if w_x is None else _f32c(w_x.to(device))
+    wy = None if w_y is None else _f32c(w_y.to(device))
     u, v = torch.empty(n, dtype=torch.float32, device=device), torch.empty(m, dtype=torch.float32, device=device)
     cxy, cyx = torch.empty(n, dtype=torch.int32, device=device), torch.empty(m, dtype=torch.int32, device=device)
     ws = torch.empty(max(lib.sdeng_sinkhorn_workspace_bytes(n, m, d, 1 if materialise else 0), 16), dtype=torch.uint8, device=device)
@@ -743,7 +748,7 @@ def mmd_median(X: torch.Tensor, Y: torch.Tensor):
     require_gpu(Y)
     lib = L.lib()
     device = X.device
-    xin, yin = X.detach().to(torch.float32).contiguous(), Y.detach().to(device, torch.float32).contiguous()
+    xin, yin = _f32c(X), _f32c(Y.to(device))
     (n, d), m = xin.shape, yin.shape[0]
     out = torch.empty(2, dtype=torch.float32, device=device)
     ws = torch.empty(max(lib.sdeng_mmd_median_workspace_bytes(n, d), 16), dtype=torch.uint8, device=device)
@@ -791,34 +796,58 @@ def langevin_moves(target, prior, x, lp, grad, step, n_moves, *, t=None, keep_fr
     return samples, acc, last
 
 
+def _net_only_desc(ctrl, t_unique: torch.Tensor, n_times: int, d: int, device, keep: list, who="ctrl_vjp", own_workspace=False):
+    """The descriptor sdeng_ctrl_vjp reads -- the drift net of a ClippedCtrl, a coefficient table that holds only the ``n_times`` times (column 0),
+    the shared workspace or one of its ``own`` (its weight images then survive other engine calls) -> (desc, coef, workspace), for the caller to keep alive."""
+    desc = L.Desc()
+    desc.abi_version = L.ABI_VERSION
+    desc.net = net_desc(ctrl, device, keep)
+    if desc.net.ctrl_kind != L.CTRL_CLIPPED:
+        raise UnsupportedByEngine(f"{who}: ClippedCtrl only")
+    desc.d = d
+    coef = torch.zeros(n_times, L.NCOEF, dtype=torch.float32, device=device)
+    coef[:, 0] = t_unique.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    desc.coef = coef.data_ptr()
+    need = L.lib().sdeng_ctrl_vjp_workspace_bytes(d, n_times)
+    ws = torch.empty(need, dtype=torch.uint8, device=device) if own_workspace else _WS.get(need, device)
+    desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
+    return desc, coef, ws
+
+
+class _RowArrays:
+    """The per-row arrays the three training kernels write and the parameter gradients are built from (include/sdeng.h): the drift net's
+    activations a0, a1, a2 and cotangents d0, d1, d2 [rows, 64] and ``dout`` [rows, d], next to the states ``x`` [rows, d] they belong to."""
+
+    def __init__(self, x: torch.Tensor):
+        self.x = x
+        self.hid = torch.empty(6, x.shape[0], 64, dtype=torch.float32, device=x.device)
+        self.dout = torch.empty_like(x)
+
+    def pointers(self, first_row=0, d=0):  # a0 .. d2, dout from row ``first_row`` on: sdeng_ctrl_vjp's arguments, the fields of an Adjoint / CmcdAdjoint
+        return [self.hid[i].data_ptr() + 4 * 64 * first_row for i in range(6)] + [self.dout.data_ptr() + 4 * d * first_row]
+
+    def into(self, adj):
+        adj.a0, adj.a1, adj.a2, adj.d0, adj.d1, adj.d2, adj.dout = self.pointers()
+
+    def result(self, gx=None, **more):
+        h = self.hid
+        return dict(x=self.x, a0=h[0], a1=h[1], a2=h[2], d0=h[3], d1=h[4], d2=h[5], dout=self.dout, gx=gx, **more)
+
+
 def ctrl_vjp(ctrl, t_unique: torch.Tensor, xs: torch.Tensor, cot: torch.Tensor, want_gx=False):
     """sdeng_ctrl_vjp: fused forward + backward of a ClippedCtrl / FourierMLP over all (time, state) rows.  ``xs`` and ``cot`` are
     [N, B, d] (states at the N times ``t_unique`` and the cotangent of the control there).  Returns the per-row arrays the parameter
     gradients are built from (include/sdeng.h): dict(a0, a1, a2, d0, d1, d2 [N*B, 64], dout [N*B, d], gx [N*B, d] or None)."""
     require_gpu(xs)
-    lib = L.lib()
     device, keep = xs.device, []
     N, B, d = xs.shape
-    desc = L.Desc()
-    desc.abi_version = L.ABI_VERSION
-    desc.net = net_desc(ctrl, device, keep)
-    if desc.net.ctrl_kind != L.CTRL_CLIPPED:
-        raise UnsupportedByEngine("ctrl_vjp: ClippedCtrl only")
-    desc.d = d
-    coef = torch.zeros(N, L.NCOEF, dtype=torch.float32, device=device)
-    coef[:, 0] = t_unique.detach().to(device=device, dtype=torch.float32).reshape(-1)
-    desc.coef = coef.data_ptr()
-    x2 = xs.detach().to(torch.float32).contiguous().view(N * B, d)
-    c2 = cot.detach().to(torch.float32).contiguous().view(N * B, d)
-    hid = torch.empty(6, N * B, 64, dtype=torch.float32, device=device)
-    dout = torch.empty(N * B, d, dtype=torch.float32, device=device)
+    desc, coef, ws = _net_only_desc(ctrl, t_unique, N, d, device, keep)
+    rows = _RowArrays(_f32c(xs).view(N * B, d))
+    c2 = _f32c(cot).view(N * B, d)
     gx = torch.empty(N * B, d, dtype=torch.float32, device=device) if want_gx else None
-    ws = _WS.get(lib.sdeng_ctrl_vjp_workspace_bytes(d, N), device)
-    desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
-    L.check(lib.sdeng_ctrl_vjp(C.byref(desc), N, B, x2.data_ptr(), c2.data_ptr(), hid[0].data_ptr(), hid[1].data_ptr(), hid[2].data_ptr(),
-                               hid[3].data_ptr(), hid[4].data_ptr(), hid[5].data_ptr(), dout.data_ptr(), gx.data_ptr() if want_gx else None,
-                               None, _stream_ptr(device)))
-    return dict(x=x2, a0=hid[0], a1=hid[1], a2=hid[2], d0=hid[3], d1=hid[4], d2=hid[5], dout=dout, gx=gx)
+    L.check(L.lib().sdeng_ctrl_vjp(C.byref(desc), N, B, rows.x.data_ptr(), c2.data_ptr(), *rows.pointers(), gx.data_ptr() if want_gx else None,
+                                   None, _stream_ptr(device)))
+    return rows.result(gx=gx)
 
 
 class VjpSession:
@@ -830,49 +859,34 @@ class VjpSession:
     def __init__(self, ctrl, t_unique: torch.Tensor, xs: torch.Tensor):
         require_gpu(xs)
         self.lib, self.device, self.keep = L.lib(), xs.device, []
-        self.N, self.B, self.d = xs.shape
-        N, B, d = xs.shape
-        self.desc = L.Desc()
-        self.desc.abi_version = L.ABI_VERSION
-        self.desc.net = net_desc(ctrl, self.device, self.keep)
-        if self.desc.net.ctrl_kind != L.CTRL_CLIPPED:
-            raise UnsupportedByEngine("ctrl_vjp: ClippedCtrl only")
-        self.desc.d = d
-        self.coef = torch.zeros(N, L.NCOEF, dtype=torch.float32, device=self.device)
-        self.coef[:, 0] = t_unique.detach().to(device=self.device, dtype=torch.float32).reshape(-1)
-        self.x = xs.detach().to(torch.float32).contiguous().view(N * B, d)
-        self.hid = torch.empty(6, N * B, 64, dtype=torch.float32, device=self.device)
-        self.dout = torch.empty(N * B, d, dtype=torch.float32, device=self.device)
+        self.N, self.B, self.d = N, B, d = xs.shape
+        self.desc, self.coef, self.ws = _net_only_desc(ctrl, t_unique, N, d, self.device, self.keep, own_workspace=True)  # its own: the images must survive
+        self.rows = _RowArrays(_f32c(xs).view(N * B, d))
         self.gx = torch.empty(B, d, dtype=torch.float32, device=self.device)
-        self.ws = torch.empty(self.lib.sdeng_ctrl_vjp_workspace_bytes(d, N), dtype=torch.uint8, device=self.device)  # its own: the images must survive
-        self.desc.workspace, self.desc.workspace_bytes = self.ws.data_ptr(), self.ws.numel()
         self.packed = False
 
     def forward_u(self) -> torch.Tensor:
         u = torch.empty(self.N * self.B, self.d, dtype=torch.float32, device=self.device)
         self.desc.coef, self.desc.flags = self.coef.data_ptr(), 0
-        L.check(self.lib.sdeng_ctrl_vjp(C.byref(self.desc), self.N, self.B, self.x.data_ptr(), None, None, None, None, None, None, None, None, None,
+        L.check(self.lib.sdeng_ctrl_vjp(C.byref(self.desc), self.N, self.B, self.rows.x.data_ptr(), None, None, None, None, None, None, None, None, None,
                                         u.data_ptr(), _stream_ptr(self.device)))
         self.packed = True
         return u.view(self.N, self.B, self.d)
 
     def step(self, k: int, cot: torch.Tensor) -> torch.Tensor:
         B, d = self.B, self.d
-        c = cot.detach().to(torch.float32).contiguous()
+        c = _f32c(cot)
         self.keep.append(c)
         self.desc.coef = self.coef.data_ptr() + 4 * L.NCOEF * k
         self.desc.flags = L.FLAG_REUSE_PACK if self.packed else 0
-        row = lambda t, width: t.data_ptr() + 4 * width * B * k  # noqa: E731
-        L.check(self.lib.sdeng_ctrl_vjp(C.byref(self.desc), 1, B, row(self.x, d), c.data_ptr(), row(self.hid[0], 64), row(self.hid[1], 64),
-                                        row(self.hid[2], 64), row(self.hid[3], 64), row(self.hid[4], 64), row(self.hid[5], 64), row(self.dout, d),
+        L.check(self.lib.sdeng_ctrl_vjp(C.byref(self.desc), 1, B, self.rows.x.data_ptr() + 4 * d * B * k, c.data_ptr(), *self.rows.pointers(B * k, d),
                                         self.gx.data_ptr(), None, _stream_ptr(self.device)))
         self.packed = True
         self.keep.clear()
         return self.gx
 
     def arrays(self):
-        h = self.hid
-        return dict(x=self.x, a0=h[0], a1=h[1], a2=h[2], d0=h[3], d1=h[4], d2=h[5], dout=self.dout, gx=None)
+        return self.rows.result()
 
 
 def diagonal_reference(kind, utils) -> bool:
@@ -950,51 +964,37 @@ def kl_adjoint(ctrl, coef: torch.Tensor, xs: torch.Tensor, z, w: torch.Tensor, l
     desc.ref = ref_desc(ref[0], ref[1], device, keep)
     if desc.ref.kind not in (L.REF_NONE, L.REF_GAUSS_DIAG, L.REF_GMM_DIAG):
         raise UnsupportedByEngine("kl_adjoint: diagonal references only")
-    cf = coef.detach().to(device=device, dtype=torch.float32).contiguous()
+    cf = _f32c(coef.to(device=device))
     desc.coef = cf.data_ptr()
-    x = xs.detach().to(torch.float32).contiguous().view(N * B, d)
-    hid = torch.empty(6, N * B, 64, dtype=torch.float32, device=device)
-    dout = torch.empty(N * B, d, dtype=torch.float32, device=device)
+    rows = _RowArrays(_f32c(xs).view(N * B, d))
     lam0 = torch.empty(B, d, dtype=torch.float32, device=device)
-    wv = w.detach().to(torch.float32).contiguous().view(B)
-    ln = lam_n.detach().to(torch.float32).contiguous()
-    zz = z.detach().to(torch.float32).contiguous() if (ito and z is not None) else None
+    wv, ln = _f32c(w).view(B), _f32c(lam_n)
+    zz = _f32c(z) if (ito and z is not None) else None
     ws = _WS.get(lib.sdeng_kl_adjoint_workspace_bytes(C.byref(desc)), device)
     desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
     adj = L.Adjoint()
-    adj.xs, adj.noise, adj.w, adj.lam_in, adj.lam_out = x.data_ptr(), (zz.data_ptr() if zz is not None else None), wv.data_ptr(), ln.data_ptr(), lam0.data_ptr()
-    adj.a0, adj.a1, adj.a2, adj.d0, adj.d1, adj.d2 = (hid[i].data_ptr() for i in range(6))
-    adj.dout = dout.data_ptr()
+    adj.xs, adj.noise, adj.w, adj.lam_in, adj.lam_out = rows.x.data_ptr(), (zz.data_ptr() if zz is not None else None), wv.data_ptr(), ln.data_ptr(), lam0.data_ptr()
+    rows.into(adj)
     dst = torch.empty(N, B, dtype=torch.float32, device=device) if score else None
     if score:
         adj.dst, adj.detach_score = dst.data_ptr(), int(bool(ctrl.detach_score))
         adj.score = ext_score.data_ptr() if ext_score is not None else None
     L.check(lib.sdeng_kl_adjoint(C.byref(desc), C.byref(adj), _stream_ptr(device)))
-    return dict(x=x, a0=hid[0], a1=hid[1], a2=hid[2], d0=hid[3], d1=hid[4], d2=hid[5], dout=dout, gx=None, dst=dst), lam0
+    return rows.result(dst=dst), lam0
 
 
 def ctrl_forward_rows(ctrl, t_unique: torch.Tensor, xs: torch.Tensor) -> torch.Tensor:
     """u = ctrl(t_k, xs[k]) for a ClippedCtrl over all rows of ``xs`` [M,B,d] in one launch (sdeng_ctrl_vjp without a cotangent): [M,B,d]."""
     require_gpu(xs)
-    lib = L.lib()
     device, keep = xs.device, []
     M, B, d = xs.shape
-    desc = L.Desc()
-    desc.abi_version = L.ABI_VERSION
-    desc.net = net_desc(ctrl, device, keep)
-    if desc.net.ctrl_kind != L.CTRL_CLIPPED:
-        raise UnsupportedByEngine("ctrl_forward_rows: ClippedCtrl only")
-    desc.d = d
-    coef = torch.zeros(M, L.NCOEF, dtype=torch.float32, device=device)
-    coef[:, 0] = t_unique.detach().to(device=device, dtype=torch.float32).reshape(-1)
-    desc.coef = coef.data_ptr()
-    x2 = xs.detach().to(torch.float32).contiguous().view(M * B, d)
+    desc, coef, ws = _net_only_desc(ctrl, t_unique, M, d, device, keep, who="ctrl_forward_rows")
+    x2 = _f32c(xs).view(M * B, d)
     u = torch.empty(M * B, d, dtype=torch.float32, device=device)
-    ws = _WS.get(lib.sdeng_ctrl_vjp_workspace_bytes(d, M), device)
-    desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
-    L.check(lib.sdeng_ctrl_vjp(C.byref(desc), M, B, x2.data_ptr(), None, None, None, None, None, None, None, None, None, u.data_ptr(),
-                               _stream_ptr(device)))
+    L.check(L.lib().sdeng_ctrl_vjp(C.byref(desc), M, B, x2.data_ptr(), None, None, None, None, None, None, None, None, None, u.data_ptr(),
+                                   _stream_ptr(device)))
     return u.view(M, B, d)
+
 
 
 _DIAG_TARGETS = ("GMM", "TwoModes", "ManyModes", "BracketTwoModes", "Gauss")
@@ -1064,34 +1064,30 @@ def cmcd_kl_adjoint(ctrl, sde, coef: torch.Tensor, xs: torch.Tensor, cbar: torch
     desc.prior = dist_desc(prior, device, keep)
     desc.cmcd_g = scalar_of(sde.diff_coeff)
     desc.cmcd_clip = scalar_of(sde.clip_score) if sde.clip_score else 0.0
-    x = xs.detach().to(torch.float32).contiguous().view(M * B, d)
+    rows = _RowArrays(_f32c(xs).view(M * B, d))
     if _name(target) in _GRAPHLESS_SCORE and score_ext is None:
-        _, score_ext = dist_eval(target, x, want_logp=False, want_score=True)
+        _, score_ext = dist_eval(target, rows.x, want_logp=False, want_score=True)
     if score_ext is not None:
-        score_ext = score_ext.detach().to(torch.float32).contiguous()
+        score_ext = _f32c(score_ext)
         if tuple(score_ext.shape) != (M * B, d):
             raise ValueError(f"cmcd_kl_adjoint: score_ext {tuple(score_ext.shape)}, want {(M * B, d)}")
-    cf = coef.detach().to(device=device, dtype=torch.float32).contiguous()
+    cf = _f32c(coef.to(device=device))
     desc.coef = cf.data_ptr()
-    cb = cbar.detach().to(torch.float32).contiguous()
-    hid = torch.empty(6, M * B, 64, dtype=torch.float32, device=device)
-    dout = torch.empty(M * B, d, dtype=torch.float32, device=device)
+    cb = _f32c(cbar)
     lam0 = torch.empty(B, d, dtype=torch.float32, device=device)
-    wv = w.detach().to(torch.float32).contiguous().view(B)
-    ln = lam_n.detach().to(torch.float32).contiguous()
+    wv, ln = _f32c(w).view(B), _f32c(lam_n)
     ws = _WS.get(lib.sdeng_cmcd_kl_adjoint_workspace_bytes(C.byref(desc)), device)
     desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
     adj = L.CmcdAdjoint()
-    adj.xs, adj.cbar, adj.w, adj.lam_in, adj.lam_out = x.data_ptr(), cb.data_ptr(), wv.data_ptr(), ln.data_ptr(), lam0.data_ptr()
-    adj.a0, adj.a1, adj.a2, adj.d0, adj.d1, adj.d2 = (hid[i].data_ptr() for i in range(6))
-    adj.dout = dout.data_ptr()
+    adj.xs, adj.cbar, adj.w, adj.lam_in, adj.lam_out = rows.x.data_ptr(), cb.data_ptr(), wv.data_ptr(), ln.data_ptr(), lam0.data_ptr()
+    rows.into(adj)
     score = desc.net.ctrl_kind != L.CTRL_CLIPPED
     dst = torch.empty(M, B, dtype=torch.float32, device=device) if score else None
     if score:
         adj.dst, adj.detach_score = dst.data_ptr(), int(bool(ctrl.detach_score))
     adj.score = score_ext.data_ptr() if score_ext is not None else None
     L.check(lib.sdeng_cmcd_kl_adjoint(C.byref(desc), C.byref(adj), _stream_ptr(device)))
-    return dict(x=x, a0=hid[0], a1=hid[1], a2=hid[2], d0=hid[3], d1=hid[4], d2=hid[5], dout=dout, gx=None, dst=dst), lam0
+    return rows.result(dst=dst), lam0
 
 
 def ctrl_forward(ctrl, t: float, x: torch.Tensor, score_gain=1.0, lerp_w=0.0):
@@ -1105,7 +1101,7 @@ def ctrl_forward(ctrl, t: float, x: torch.Tensor, score_gain=1.0, lerp_w=0.0):
     tgt, prior = ctrl_target(ctrl)
     desc.target = dist_desc(tgt, device, keep)
     desc.prior = dist_desc(prior, device, keep)
-    xin = x.detach().to(torch.float32).contiguous()
+    xin = _f32c(x)
     desc.B, desc.d, desc.N = xin.shape[0], xin.shape[1], 1
     out = torch.empty_like(xin)
     need = lib.sdeng_workspace_bytes(C.byref(desc))

@@ -9,8 +9,9 @@ What is on the HIP path: the eval / sampling direction (``change_sde_ctrl=False`
 ``Trainable.evaluate`` times as ``eval/sample_time`` (solver/oc.py:148-158); ``x`` may be an ``engine.InitialDraw`` (x0 drawn by the
 kernel) and ``loss.dist`` a torch.distributed module (sharded run: global estimators and weights).  ``compute_eubo`` (the noising loops of
 SURVEY.md 8f-2) is a HIP launch too (RDS losses, DiscreteTimeReversalLossEI, CMCD on mixture targets).  The training direction (``__call__``,
-8f-1) is built for the log-variance methods (``_lv_loss``: HIP step loop + one batched autograd pass of the control); KL
-training raises instead of silently running a PyTorch loop.
+8f-1): the HIP step loop for the value; the gradient from one batched pass of the control for the log-variance methods (``_lv_loss``) and
+from the discrete adjoint of the step loop for the KL methods (``_kl_loss``, ``_kl_loss_cmcd``).  What those calls share -- the rollout, the KL
+weights, the parameter gradients from a kernel's per-row arrays, the hand-off to autograd, the adjoints themselves -- is ``losses/training.py``.
 
 Extra, engine-only knobs (keyword-only, default to the reference behaviour):
   * ``noise=[N,B,d]`` injects the normals (replays the reference's ``randn_like`` stream, parity mode);
@@ -27,140 +28,8 @@ import torch
 from .. import _lib as L
 from .. import engine as E
 from ..utils.common import Results, make_results
-
-
-def ctrl_batched(ctrl, t_unique: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    """``ctrl(t, x)`` (with autograd) for M distinct times and B states per time, x [M,B,d] -> [M*B,d].  Same operations
-    as the modules' own forward (models/mlp.py, models/reparam.py), except that the time embeddings -- functions of t only --
-    are evaluated once per distinct time instead of once per row (the reference recomputes them for every particle,
-    models/mlp.py:136-137); other control types fall back to the plain per-row call."""
-    from ..models.reparam import _clip
-    M, B, d = x.shape
-    flat = x.reshape(M * B, d)
-    t_rows = t_unique.repeat_interleave(B).view(-1, 1)
-    name, net = type(ctrl).__name__, getattr(ctrl, "base_model", None)
-    if name not in ("ClippedCtrl", "ScoreCtrl", "LerpCtrl", "CancelDriftCtrl") or type(net).__name__ != "FourierMLP":
-        return ctrl(t_rows, flat)
-    h = net.input_embed(flat) + net.timestep_embed(t_unique.view(-1, 1)).repeat_interleave(B, dim=0)
-    for layer in net.hidden_layer:
-        h = layer(net.activation(h))
-    out = _clip(net.out_layer(net.activation(h)), ctrl.clip_model)
-    if name == "ClippedCtrl":
-        return out
-    if name in ("ScoreCtrl", "CancelDriftCtrl"):
-        score = ctrl.scale_score * ctrl.clipped_target_score(t_rows, flat)
-    else:
-        score = ctrl.scale_score * ctrl.clipped_interpolated_score(t_rows, flat)
-    if ctrl.score_model is not None:
-        score = score * _clip(ctrl.score_model(t_unique.view(-1, 1)), ctrl.clip_model).repeat_interleave(B, dim=0)
-    if name == "CancelDriftCtrl":  # reparam.py:142-145
-        g, f = ctrl.sde.diff(t_rows, flat), ctrl.sde.drift(t_rows, flat)
-        return out + (f / g) + 0.5 * g * score if ctrl.use_rescaling else out + (f / torch.square(g)) + 0.5 * score
-    return out + (ctrl.sde.diff(t_rows, flat) * score if name == "LerpCtrl" else score)
-
-
-class _FusedIntegral(torch.autograd.Function):
-    """s_b = sum_k <u_theta(t_k, x_kb), zc_kb> for a ClippedCtrl over a FourierMLP, with the gradient w.r.t. the net's parameters from
-    ONE fused HIP forward + backward over all N * B rows (``sdeng_ctrl_vjp``, csrc/grad_kernel.hpp) and six skinny GEMMs -- instead of
-    the ~150 small kernels of the eager torch pass.  The VALUE of s is not needed by the losses (it enters as ``s - s.detach()``), so
-    ``forward`` returns zeros and all the work happens in ``backward``, where the cotangent of s_b (one number per particle) is known."""
-
-    @staticmethod
-    def forward(ctx, ctrl, t_unique, xs, zc, *params):
-        ctx.ctrl, ctx.shape = ctrl, tuple(xs.shape)
-        ctx.save_for_backward(t_unique, xs, zc)
-        return torch.zeros(xs.shape[1], dtype=xs.dtype, device=xs.device)
-
-    @staticmethod
-    def backward(ctx, grad_s):
-        t_unique, xs, zc = ctx.saved_tensors
-        N, B, d = ctx.shape
-        cot = zc.view(N, B, d) * grad_s.view(1, B, 1)  # d loss / d u_kb
-        ctrl = ctx.ctrl
-        net_view = fused_net_view(ctrl)
-        grads = vjp_param_grads(net_view, t_unique, E.ctrl_vjp(net_view, t_unique, xs, cot), N, B)
-        sm = getattr(ctrl, "score_model", None)
-        sm_params = [p for p in sm.parameters() if p.requires_grad] if (net_view is not ctrl and sm is not None) else []
-        if sm_params:
-            # ScoreCtrl: u = clip(net) + scale clip(score_pi(x)) s_theta(t).  The states are constants, so the score part only reaches the
-            # score model: d loss / d s_theta(t_k) = sum_b <cot_kb, scale clip(score_pi(x_kb))> (HIP score kernel, one launch for all rows)
-            from ..models.reparam import _clip
-            _, sc = E.dist_eval(E.ctrl_target(ctrl)[0], xs.reshape(N * B, d), want_logp=False, want_score=True)
-            dst = (cot.reshape(N * B, d) * (ctrl.scale_score * _clip(sc, ctrl.clip_score))).sum(-1).view(N, B).sum(1)
-            with torch.enable_grad():
-                st = ctrl.clipped_score_model(t_unique.view(-1, 1), None).view(N)
-                sm_grads = torch.autograd.grad(st, sm_params, grad_outputs=dst, allow_unused=True)
-            grads.update({p: g for p, g in zip(sm_params, sm_grads) if g is not None})
-        params = [p for p in ctrl.parameters() if p.requires_grad]
-        return (None, None, None, None) + tuple(grads.get(p) for p in params)
-
-
-_NET_VIEWS = {}
-
-
-def fused_training_ok(ctrl) -> bool:
-    """Controls whose batched log-variance pass is the fused HIP forward + backward: ClippedCtrl over a FourierMLP, and a plain ScoreCtrl
-    over one (its score part has no state gradient to take in this pass) on a target the score kernel knows."""
-    if type(getattr(ctrl, "base_model", None)).__name__ != "FourierMLP":
-        return False
-    if type(ctrl).__name__ == "ClippedCtrl":
-        return True
-    if type(ctrl).__name__ != "ScoreCtrl" or not (ctrl.score_model is None or type(ctrl.score_model).__name__ == "TimeEmbed"):
-        return False
-    try:
-        E.dist_desc(E.ctrl_target(ctrl)[0], "cpu", [])
-    except E.UnsupportedByEngine:
-        return False
-    return True
-
-
-def fused_net_view(ctrl):
-    """The ClippedCtrl part of a ScoreCtrl (same drift net, same clip) as sdeng_ctrl_vjp wants it; a ClippedCtrl is its own view."""
-    if type(ctrl).__name__ == "ClippedCtrl":
-        return ctrl
-    view = _NET_VIEWS.get(id(ctrl))
-    if view is None or view[0]() is not ctrl or view[1].clip_model != ctrl.clip_model:
-        import weakref
-
-        from ..models.reparam import ClippedCtrl
-        view = (weakref.ref(ctrl), ClippedCtrl(base_model=ctrl.base_model, clip_model=ctrl.clip_model))
-        _NET_VIEWS[id(ctrl)] = view
-    return view[1]
-
-
-def vjp_param_grads(ctrl, t_unique, r, N, B):
-    """Per-row arrays of ``sdeng_ctrl_vjp`` (include/sdeng.h) -> {parameter: gradient} for a ClippedCtrl over a FourierMLP."""
-    net = ctrl.base_model
-
-    def outer(dl, act):
-        # dl^T act over all N * B rows.  As ONE GEMM this is 64 x 64 (or d x 64) with K = N * B: hipBLASLt runs it on a handful of
-        # workgroups (180 us each at 512 x 100 rows, rocprofv3); batched over the N times and summed it fills the chip (~10 us).
-        return torch.bmm(dl.view(N, B, -1).transpose(1, 2), act.view(N, B, -1)).sum(0)
-    grads = {net.out_layer.weight: outer(r["dout"], r["a2"]), net.out_layer.bias: r["dout"].sum(0),
-             net.hidden_layer[1].weight: outer(r["d2"], r["a1"]), net.hidden_layer[1].bias: r["d2"].sum(0),
-             net.hidden_layer[0].weight: outer(r["d1"], r["a0"]), net.hidden_layer[0].bias: r["d1"].sum(0),
-             net.input_embed.weight: outer(r["d0"], r["x"]), net.input_embed.bias: r["d0"].sum(0)}
-    # time embedding e_t = timestep_embed(t_k): its cotangent is the sum over the particles of d0; the small module itself (2 layers on
-    # N rows) is differentiated by torch
-    te_params = [p for p in net.timestep_embed.parameters() if p.requires_grad]
-    if te_params:
-        with torch.enable_grad():
-            e = net.timestep_embed(t_unique.view(-1, 1))
-            te_grads = torch.autograd.grad(e, te_params, grad_outputs=r["d0"].view(N, B, 64).sum(1), allow_unused=True)
-        grads.update({p: g for p, g in zip(te_params, te_grads) if g is not None})
-    return grads
-
-
-class _IntegralPass(torch.nn.Module):
-    """s_b = sum_k <u(t_k, x_kb), zc_kb>: the one part of the log-variance loss that carries a graph (BaseOCLoss._lv_loss)."""
-
-    def __init__(self, ctrl):
-        super().__init__()
-        self.ctrl = ctrl
-
-    def forward(self, t_unique, xs, zc):
-        u = ctrl_batched(self.ctrl, t_unique, xs)
-        return (u * zc).sum(dim=-1).view(xs.shape[0], xs.shape[1]).sum(dim=0)
+from . import training as T
+from .training import _capturable, _FusedIntegral, _GraphedAdjointStep, _graphed_step, _IntegralPass, ctrl_batched, fused_net_view, fused_training_ok, vjp_param_grads  # noqa: F401  (all stay reachable here)
 
 
 class BaseOCLoss:
@@ -198,7 +67,7 @@ class BaseOCLoss:
         self.timing_events = None  # optional _lib.HipEvents: times the step-loop kernel alone
         self.graph_adjoint = True  # KL training where the adjoint runs step by step in torch (CMCD; controls / targets / references the adjoint kernel does not cover): each step replayed as a hipGraph; False: eager
         self.native_adjoint = True  # KL training of a ClippedCtrl with no / a diagonal reference: the adjoint recursion as ONE launch (sdeng_kl_adjoint; CMCD: sdeng_cmcd_kl_adjoint); False: one sdeng_ctrl_vjp per step (CMCD: one torch VJP per step)
-        self.last_adjoint_path = None  # CMCD KL training: 'native' | 'stepwise', which adjoint the last call ran
+        self.last_adjoint_path = None  # KL training, which adjoint the last call ran: 'native' (one launch) | 'fused' (sdeng_ctrl_vjp per step; not CMCD) | 'stepwise' (torch VJP per step)
         self.fused_training = True  # ClippedCtrl over a FourierMLP: the batched control pass of training as ONE fused HIP forward + backward (sdeng_ctrl_vjp); False: the eager torch pass
         self.graph_training = False  # True: the batched control pass of log-variance training (forward + backward) is replayed as a hipGraph (_IntegralPass)
         self._graphed = {}
@@ -268,11 +137,10 @@ class BaseOCLoss:
     def state_dict(self) -> dict:
         return {"n_filtered": self.n_filtered}
 
-    def _lv_loss(self, ts, x, simulate, terminal, *, lin, coef_kw=None, rnd0=None, ito=True):
+    def _lv_loss(self, ts, x, simulate, *, coef_kw=None, rnd0=None, ito=True):
         """Log-variance training value (losses/oc.py ``__call__`` of every loss, method in ('lv', 'lv_traj')).  The
         trajectories are driven by the DETACHED control (generative_and_sde_ctrl, :83-103), so the states carry no graph
-        and the step loop is exactly the eval path: it runs as one HIP launch (``simulate(x, z)`` with the trajectory and
-        the noise kept) and its log-weights ARE the loss's
+        and the step loop is exactly the eval path: it runs as one HIP launch (``simulate(x)`` with the trajectory kept) and its log-weights ARE the loss's
             rnd = rnd0 + sum_k c_k <u_k, u_k.detach() - u_k/2> + c'_k <u_k, z_k> + terminal(x_N);
         their gradient comes from ONE batched pass of the control over all N*B (time, state) pairs
         (:269-271, :284 EM; :490-491, :499 EI / DDPM-like; :957-958, :965 DIS; :1361-1383 DDS).  KL training differentiates
@@ -283,27 +151,10 @@ class BaseOCLoss:
         # alias), while the gradient below is unchanged: c'_k z_k back through the net, along the perturbed trajectory
         perturb = self._ctrl_perturbation()
         coef_kw = dict(coef_kw or {}, **perturb)
-        # a fresh stream per training call (the reference consumes torch's global generator): call c uses the engine's Philox
-        # streams keyed by seed + c * golden-ratio increment -- for the step noise AND for an x0 left to the engine (an InitialDraw
-        # materialised with the loss's fixed seed would hand every training step the same batch); call 0 is the eval stream of ``seed``
-        E.require_gpu(x)
-        seed_c = self._next_train_seed()
-        x = self._x0(x, seed_c)
-        if self.traj_per_sample != 1:
-            x = x.repeat(self.traj_per_sample, 1, 1).reshape(-1, x.shape[-1])
-        N, (B, d) = ts.numel() - 1, x.shape
+        # VALUE: the step loop already integrates exactly this rnd (the detached control is the control), terminal terms included.  (the kernel draws the normals
+        # of stream seed_c itself -- bit for bit the z below -- so small batches may take the low-latency split-tile kernel, which does not replay noise)
+        x, x_n, rnd_sim, xs, seed_c, N, B, d = T.rollout(self, ts, x, simulate, perturb=perturb)
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)
-        # VALUE: the step loop already integrates exactly this rnd (the detached control is the control), terminal terms included.
-        # (the kernel draws the normals of stream seed_c itself -- bit for bit the z above -- so nothing is injected and small
-        # batches may take the low-latency split-tile kernel, which writes the trajectory but does not replay noise)
-        seed_eval, self.seed = self.seed, seed_c
-        self._perturb = perturb
-        try:
-            with torch.no_grad():
-                x_n, rnd_sim, xs = simulate(x, None)
-        finally:
-            self.seed = seed_eval
-            self._perturb = {}
         with torch.no_grad():
             rnd_val = rnd_sim.reshape(B, 1)
             if rnd0 is not None:
@@ -369,110 +220,32 @@ class BaseOCLoss:
         host's per-step coefficients):
             lambda_N = d terminal / d x_N ;   for k = N-1 .. 0:  S_k = <lambda_{k+1}, x_{k+1}(x_k, theta)> + sum_b w_b d rnd_k,b(x_k, theta)
             lambda_k = dS_k/dx_k ,   dL/dtheta += dS_k/dtheta
-        with the HIP states x_k as constants -- N vector-Jacobian products of ONE step each (torch autograd on the control module and the
-        reference score), no graph through the loop.  This is the same number the reference's ``loss.backward()`` produces (fixtures
-        ``train_kl_*``: loss to 6 digits, gradients to fp32 round-off); it is not yet a fused kernel."""
+        with the HIP states x_k as constants, no graph through the loop.  Three adjoints (losses/training.py), named by ``last_adjoint_path``:
+        'native', the recursion as ONE launch (kl_grads_native, sdeng_kl_adjoint: DESIGN f-1); 'fused', one sdeng_ctrl_vjp per step
+        (kl_grads_fused); 'stepwise', one torch vector-Jacobian product per step (kl_grads_stepwise).  This is the same number the
+        reference's ``loss.backward()`` produces (fixtures ``train_kl_*``: loss to 6 digits, gradients to fp32 round-off)."""
         if self.sde_ctrl_noise is not None or self.sde_ctrl_dropout is not None:
             raise E.UnsupportedByEngine("sde_ctrl_noise / sde_ctrl_dropout perturb the simulated control (losses/oc.py:97-101): not built")
-        E.require_gpu(x)
-        seed_c = self._next_train_seed()
-        x = self._x0(x, seed_c)
-        if self.traj_per_sample != 1:
-            x = x.repeat(self.traj_per_sample, 1, 1).reshape(-1, x.shape[-1])
-        N, (B, d) = ts.numel() - 1, x.shape
-        seed_eval, self.seed = self.seed, seed_c
-        try:
-            with torch.no_grad():
-                x_n, rnd_sim, xs = simulate(x)
-        finally:
-            self.seed = seed_eval
+        x, x_n, rnd_sim, xs, seed_c, N, B, d = T.rollout(self, ts, x, simulate)
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)  # bit for bit the normals the kernel drew
-        rnd_val = rnd_sim.reshape(B, 1)
-        mask = self.filter(rnd_val, samples=x_n)
-        assert mask.shape == rnd_val.shape
-        self.n_filtered += (mask.numel() - mask.sum()).item()
-        w = mask.to(rnd_val.dtype) / mask.sum()  # d mean(rnd[mask]) / d rnd_b
-        value = rnd_val[mask].mean()
+        _, w, value = T.kl_weights(self, rnd_sim.reshape(B, 1), x_n)
         ctrl = self.generative_ctrl
         params = [p for p in ctrl.parameters() if p.requires_grad]
-        grads = [torch.zeros_like(p) for p in params]
         coef = self._coef(ts, x.device, **(coef_kw or {}))
-        fused = self.fused_training and type(ctrl).__name__ == "ClippedCtrl" and type(getattr(ctrl, "base_model", None)).__name__ == "FourierMLP"
         with torch.enable_grad():
             xN = x_n.detach().requires_grad_(True)
             lam, = torch.autograd.grad((w * terminal(xN).view(B, 1)).sum(), xN)
-            ref_kind = E.resolve_reference(reference_ctrl) if reference_ctrl is not None else ("none", {})
-            native = self.native_adjoint and E.adjoint_ctrl_ok(ctrl) and E.diagonal_reference(*ref_kind)
-            if native:
-                # ClippedCtrl (every RDS / LRDS solver at its defaults) or ScoreCtrl on a diagonal mixture target (DDS / PIS on the mixture
-                # benchmarks, BASELINE config 1), no / a diagonal reference: the whole recursion below is ONE launch (sdeng_kl_adjoint:
-                # lambda in registers, u recomputed, Hessian-vector products of the mixtures in closed form); the parameter gradients come
-                # from the per-row arrays, as in log-variance training, the score model's from its N cotangents.
-                arrays, _ = E.kl_adjoint(ctrl, coef, xs[:-1], z if ito else None, w, lam, lin=lin, ito=ito, ref=ref_kind)
-                found = vjp_param_grads(ctrl, coef[:, 0].contiguous(), arrays, N, B)
-                sm = getattr(ctrl, "score_model", None)
-                sm_params = [p for p in sm.parameters() if p.requires_grad] if (arrays["dst"] is not None and sm is not None) else []
-                if sm_params:
-                    st = ctrl.clipped_score_model(coef[:, 0].contiguous().view(-1, 1), None).view(N)
-                    sm_grads = torch.autograd.grad(st, sm_params, grad_outputs=arrays["dst"].sum(1), allow_unused=True)
-                    found.update({p: g for p, g in zip(sm_params, sm_grads) if g is not None})
-                grads = [found.get(p, torch.zeros_like(p)) for p in params]
-                fused = True
-            elif fused:
-                # ClippedCtrl over the FourierMLP (every RDS / LRDS solver): the control's part of each step's vector-Jacobian product is
-                # the fused HIP forward + backward of that time step (sdeng_ctrl_vjp; weights packed once per call), the reference score's
-                # part a small torch VJP; the parameter gradients come from the per-row arrays at the end, as in log-variance training.
-                sess = E.VjpSession(ctrl, coef[:, 0], xs[:-1])
-                u_all = sess.forward_u()
-                for k in range(N - 1, -1, -1):
-                    c, u, zk = coef[k], u_all[k], z[k]
-                    if lin:
-                        g = c[2] * lam + w * (2.0 * c[4] * u + (c[5] * zk if ito else 0.0))
-                    else:
-                        g = (c[2] * c[4]) * lam + w * (c[4] * u + (c[5] * zk if ito else 0.0))
-                    gx = sess.step(k, g)
-                    jl = None
-                    if reference_ctrl is not None:
-                        xk = xs[k].detach().requires_grad_(True)
-                        jl, = torch.autograd.grad((reference_ctrl(c[0], xk) * lam).sum(), xk)
-                    if lin:
-                        lam = c[1] * lam + gx if jl is None else c[1] * lam + c[2] * jl + gx
-                    else:
-                        lam = (1.0 + c[4] * c[1]) * lam + gx if jl is None else (1.0 + c[4] * c[1]) * lam + (c[4] * c[3]) * jl + gx
-                found = vjp_param_grads(ctrl, coef[:, 0].contiguous(), sess.arrays(), N, B)
-                grads = [found.get(p, torch.zeros_like(p)) for p in params]
-            def step(lam_in, x_in, z_in, c, w_in):
-                """One step of the adjoint in torch (controls / targets / references the adjoint kernel does not cover)."""
-                with torch.enable_grad():
-                    xk = x_in.detach().requires_grad_(True)
-                    u = ctrl(c[0], xk)
-                    ref = reference_ctrl(c[0], xk) if reference_ctrl is not None else None
-                    uu, uz = (u * u).sum(-1, keepdim=True), (u * z_in).sum(-1, keepdim=True)
-                    if lin:   # x' = c1 x + c2 (u [+ ref]) + c3 z ;  rnd += c4 <u,u> + c5 <u,z>
-                        x_next = c[1] * xk + c[2] * (u if ref is None else ref + u) + c[3] * z_in
-                        dr = c[4] * uu + (c[5] * uz if ito else 0.0)
-                    else:     # x' = x + ((c1 x [+ c3 ref]) + c2 u) c4 + c2 (c5 z) ;  rnd += 0.5 <u,u> c4 + c5 <u,z>
-                        drift = c[1] * xk if ref is None else c[1] * xk + c[3] * ref
-                        x_next = xk + (drift + c[2] * u) * c[4] + c[2] * (c[5] * z_in)
-                        dr = 0.5 * uu * c[4] + (c[5] * uz if ito else 0.0)
-                    got = torch.autograd.grad((lam_in * x_next).sum() + (w_in * dr).sum(), [xk] + params, allow_unused=True)
-                for acc, gk in zip(grads, got[1:]):
-                    if gk is not None:
-                        acc.add_(gk)
-                return got[0]
-
-            if not (fused or native):
-                # launch-bound (~60 small kernels per step): replayed as a hipGraph per (shape, control, form); eager if capture fails
-                runner = _graphed_step(self, ("kl", id(ctrl), id(getattr(reference_ctrl, "__self__", reference_ctrl)), B, d, bool(lin), bool(ito), str(x.device)), step, grads,
-                                            (lam, xs[0], z[0], coef[0], w)) if (self.graph_adjoint and _capturable(ctrl)) else None
-                for k in range(N - 1, -1, -1):
-                    args = (lam, xs[k], z[k], coef[k], w)
-                    lam = runner(*args) if runner is not None else step(*args)
-                if runner is not None:
-                    grads = [gr.clone() for gr in runner.grads]
-        # hand the gradient to autograd: value + sum <p - p.detach(), dL/dp>  (zero-valued, gradient dL/dp)
-        surrogate = sum(((p - p.detach()) * g).sum() for p, g in zip(params, grads))
-        return value.detach() + surrogate, {"train/n_filtered_cumulative": self.n_filtered}
+        ref_kind = E.resolve_reference(reference_ctrl) if reference_ctrl is not None else ("none", {})
+        if self.native_adjoint and E.adjoint_ctrl_ok(ctrl) and E.diagonal_reference(*ref_kind):
+            self.last_adjoint_path = "native"
+            grads = T.kl_grads_native(ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, ref_kind=ref_kind)
+        elif self.fused_training and type(ctrl).__name__ == "ClippedCtrl" and type(getattr(ctrl, "base_model", None)).__name__ == "FourierMLP":
+            self.last_adjoint_path = "fused"
+            grads = T.kl_grads_fused(ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, reference_ctrl=reference_ctrl)
+        else:
+            self.last_adjoint_path = "stepwise"
+            grads = T.kl_grads_stepwise(self, ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, reference_ctrl=reference_ctrl)
+        return T.hand_to_autograd(self, value, params, grads)
 
     # ---- engine plumbing ---------------------------------------------------------------------
     @staticmethod
@@ -668,16 +441,15 @@ class EMReferenceSDELoss(BaseOCLoss):
 
     def __call__(self, ts, x, terminal_unnorm_log_prob, reference_log_prob):
         """[TRAINING] losses/oc.py:364-394 (see BaseOCLoss._lv_loss)."""
-        def sim(xx, z):
+        def sim(xx):
             return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                                 change_sde_ctrl=False, return_traj=True, use_ema=False, noise=z)
+                                 change_sde_ctrl=False, return_traj=True, use_ema=False)
         with_ref = E.resolve_reference(self.reference_ctrl)[0] != "none"
         if self.method in ("kl", "kl_ito"):  # :364-394 with change_sde_ctrl = False; the Ito term is always part of these losses (:284, :499)
-            return self._kl_loss(ts, x, lambda xx: sim(xx, None),
+            return self._kl_loss(ts, x, sim,
                                  lambda xn: reference_log_prob(xn).view(-1, 1) - terminal_unnorm_log_prob(xn).view(-1, 1),
                                  lin=self.kind != "em", coef_kw=dict(with_ref=with_ref), reference_ctrl=self.reference_ctrl if with_ref else None)
-        return self._lv_loss(ts, x, sim, lambda xn: self._logp(reference_log_prob, xn) - self._logp(terminal_unnorm_log_prob, xn),
-                             lin=self.kind != "em", coef_kw=dict(with_ref=with_ref))
+        return self._lv_loss(ts, x, sim, coef_kw=dict(with_ref=with_ref))
 
     def compute_eubo(self, ts, x, terminal_unnorm_log_prob, reference_log_prob, use_ema=False, *, noise=None):
         """losses/oc.py:298-362 (EM; inherited by the DDPM-like loss) and :512-568 (EI): noising trajectories started at
@@ -794,7 +566,6 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
                                   noise=noise, eubo=True)
         return rnd
 
-
     def __call__(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None):
         """[TRAINING] losses/oc.py:830-857, log-variance methods.  The trajectory is driven by the detached control
         (:704-705, :722), so it is the eval trajectory: one HIP launch (trajectory and noise kept).  The target / prior
@@ -804,18 +575,11 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         with b_k = drift(t_k, x_k), b'_k = drift(t_{k+1}, x_{k+1})."""
         if self.sde_ctrl_noise is not None or self.sde_ctrl_dropout is not None:
             raise E.UnsupportedByEngine("sde_ctrl_noise / sde_ctrl_dropout perturb the simulated control: not built")
-        E.require_gpu(x)
         if self.method in ("kl", "kl_ito"):
             return self._kl_loss_cmcd(ts, x, terminal_unnorm_log_prob, initial_log_prob)
-        seed_c = self._next_train_seed()
-        x = self._x0(x, seed_c)
-        if self.traj_per_sample != 1:
-            x = x.repeat(self.traj_per_sample, 1, 1).reshape(-1, x.shape[-1])
-        N, (B, d) = ts.numel() - 1, x.shape
+        x, _, _, _, seed_c, N, B, d = T.rollout(self, ts, x)  # (the step loop below replays the injected z on the eval stream: no seed swap)
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)
-        target = getattr(self.sde.target_score, "__self__", None)
-        prior = getattr(self.sde.prior_score, "__self__", None)
-        g, T = float(self.sde.diff_coeff), float(self.sde.terminal_t)
+        g = float(self.sde.diff_coeff)
         with torch.no_grad():
             x_n, _, xs = self.simulate(ts, x, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False,
                                        return_traj=True, use_ema=False, noise=z)
@@ -831,7 +595,6 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         rnd = (0.5 * (cost ** 2).sum(-1) * dt.view(N, 1) + (cost * (u[:-1].detach() - u[:-1])).sum(-1) * dt.view(N, 1)
                + (cost * db).sum(-1)).sum(0).view(B, 1) + const
         return self.compute_loss(rnd, samples=x_n)
-
 
     def _cmcd_drifts(self, coef, xs):
         """The annealed drift b_j = clip(0.5 g^2 (tau_j s_pi(x_j) + (1 - tau_j) s_prior(x_j))) (eq/sdes.py:101-110) at all N + 1 evaluation points
@@ -874,64 +637,37 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         """[TRAINING] KL methods of CMCD (losses/oc.py:830-857 on simulate(train=True): rnd0 = 0, :695-699; the un-detached control drives
         the SDE, :706-709).  VALUE: the HIP step loop (its log-weight minus the initial log-density it adds).  GRADIENT: the discrete
         adjoint of the reference's own step (:711-742) -- y = x + (b_s(x) + g u_s(x)) dt + g db, cost = (b_s(x) + b_t(y))/g + u_s(x) - u_t(y),
-        rnd += 0.5 |cost|^2 dt + <cost, db> -- one torch vector-Jacobian product per step over the HIP states (two control evaluations
-        share the state y, so the step is differentiated as a whole; the target / prior scores are differentiated exactly where the
-        reference's are: closed-form scores carry a graph, autograd-made ones do not, distr/base.py:146-154)."""
-        seed_c = self._next_train_seed()
-        x = self._x0(x, seed_c)
-        if self.traj_per_sample != 1:
-            x = x.repeat(self.traj_per_sample, 1, 1).reshape(-1, x.shape[-1])
-        N, (B, d) = ts.numel() - 1, x.shape
-        seed_eval, self.seed = self.seed, seed_c
-        try:
-            with torch.no_grad():
-                x_n, rnd_sim, xs = self.simulate(ts, x, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False, return_traj=True)
-        finally:
-            self.seed = seed_eval
+        rnd += 0.5 |cost|^2 dt + <cost, db> -- over the HIP states: as ONE launch where sdeng_cmcd_kl_adjoint covers the loss
+        (``last_adjoint_path`` 'native'), else one torch vector-Jacobian product per step ('stepwise': two control evaluations share the
+        state y, so the step is differentiated as a whole; the target / prior scores are differentiated exactly where the reference's are:
+        closed-form scores carry a graph, autograd-made ones do not, distr/base.py:146-154).  The shared pieces: losses/training.py."""
+        x, x_n, rnd_sim, xs, seed_c, N, B, d = T.rollout(self, ts, x, lambda xx: self.simulate(
+            ts, xx, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False, return_traj=True))
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)  # bit for bit the normals the kernel drew
-        rnd_val = rnd_sim.reshape(B, 1) - self._logp(initial_log_prob, x)  # (the evaluation pass starts from log p_prior(x0), training from 0)
-        mask = self.filter(rnd_val, samples=x_n)
-        assert mask.shape == rnd_val.shape
-        self.n_filtered += (mask.numel() - mask.sum()).item()
-        w = mask.to(rnd_val.dtype) / mask.sum()
-        value = rnd_val[mask].mean()
+        _, w, value = T.kl_weights(self, rnd_sim.reshape(B, 1) - self._logp(initial_log_prob, x), x_n)  # (the evaluation pass starts from log p_prior(x0), training from 0)
         ctrl = self.generative_ctrl
         params = [p for p in ctrl.parameters() if p.requires_grad]
-        grads = [torch.zeros_like(p) for p in params]
         g = self.sde.diff_coeff
-        tdev = ts.to(x.device)
-        def terminal_cotangent():
-            """d (sum_b w_b (-log pi~(x_N,b))) / d x_N.  A piecewise-constant density (the checkerboard) builds no graph to x_N: its terminal
-            term contributes nothing to the reference's backward() either."""
-            with torch.enable_grad():
-                xN = x_n.detach().requires_grad_(True)
-                out = (w * (-terminal_unnorm_log_prob(xN).view(B, 1))).sum()
-                return torch.autograd.grad(out, xN)[0] if out.requires_grad else torch.zeros_like(xN)
+        # lambda_N = d (sum_b w_b (-log pi~(x_N,b))) / d x_N.  A piecewise-constant density (the checkerboard) builds no graph to x_N: its
+        # terminal term contributes nothing to the reference's backward() either.
+        with torch.enable_grad():
+            xN = x_n.detach().requires_grad_(True)
+            out = (w * (-terminal_unnorm_log_prob(xN).view(B, 1))).sum()
+            lam = torch.autograd.grad(out, xN)[0] if out.requires_grad else torch.zeros_like(xN)
 
         if self.native_adjoint and E.cmcd_adjoint_ok(self):
             # ClippedCtrl / ScoreCtrl, diagonal or isotropic prior, mixture / phi^4 / logistic-regression target: the recursion over the
             # N + 1 evaluation points is ONE launch (sdeng_cmcd_kl_adjoint); its input, the per-step cost cotangents, is one batched
             # forward pass over the HIP states.  Parameter gradients from the per-row arrays, as in _kl_loss.
             self.last_adjoint_path = "native"
-            lam = terminal_cotangent()
             coef = self._coef(ts, x.device)
-            t_all = coef[:, 0].contiguous()
             with torch.no_grad():
                 cbar, s_tgt = self._cmcd_step_costs(ctrl, coef, xs, z)
             graphless = type(getattr(self.sde.target_score, "__self__", None)).__name__ in E._GRAPHLESS_SCORE
             arrays, _ = E.cmcd_kl_adjoint(ctrl, self.sde, coef, xs, cbar, w, lam, score_ext=s_tgt if graphless else None)
-            with torch.enable_grad():
-                found = vjp_param_grads(ctrl, t_all, arrays, N + 1, B)
-                sm = getattr(ctrl, "score_model", None)
-                sm_params = [p for p in sm.parameters() if p.requires_grad] if (arrays["dst"] is not None and sm is not None) else []
-                if sm_params:
-                    st = ctrl.clipped_score_model(t_all.view(-1, 1), None).view(N + 1)
-                    sm_grads = torch.autograd.grad(st, sm_params, grad_outputs=arrays["dst"].sum(1), allow_unused=True)
-                    found.update({p: gr for p, gr in zip(sm_params, sm_grads) if gr is not None})
-            grads = [found.get(p, torch.zeros_like(p)) for p in params]
-            surrogate = sum(((p - p.detach()) * gr).sum() for p, gr in zip(params, grads))
-            return value.detach() + surrogate, {"train/n_filtered_cumulative": self.n_filtered}
+            return T.hand_to_autograd(self, value, params, T.param_grads(ctrl, coef[:, 0].contiguous(), arrays, N + 1, B, params))
         self.last_adjoint_path = "stepwise"
+        grads = [torch.zeros_like(p) for p in params]
 
         def step(lam_in, x_in, z_in, s, t, w_in):
             """One step of the adjoint: lambda_k and the parameter-gradient contributions of step k (accumulated into ``grads``)."""
@@ -949,97 +685,10 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
                     acc.add_(gk)
             return got[0]
 
-        lam = terminal_cotangent()
-        # The ~130 small kernels of one step are launch-bound (2048 x 100: 5 ms per step of the recursion): the step is captured once per
-        # (shape, control) as a hipGraph and replayed N times; a capture that fails runs the steps eagerly, and says so.
-        runner = _graphed_step(self, ("cmcd", id(ctrl), B, d, str(x.device)), step, grads,
-                                    (lam, xs[0], z[0], tdev[0], tdev[1], w)) if (self.graph_adjoint and _capturable(ctrl, self.sde.target_score)) else None
-        for k in range(N - 1, -1, -1):
-            args = (lam, xs[k], z[k], tdev[k], tdev[k + 1], w)
-            lam = runner(*args) if runner is not None else step(*args)
-        if runner is not None:
-            grads = [gr.clone() for gr in runner.grads]
-        surrogate = sum(((p - p.detach()) * gr).sum() for p, gr in zip(params, grads))
-        return value.detach() + surrogate, {"train/n_filtered_cumulative": self.n_filtered}
-
-
-
-def _capturable(ctrl, *score_fns) -> bool:
-    """Can one adjoint step of this control be captured as a hipGraph?  Not when a score in it is the base class's autograd evaluation
-    (distr/base.py:146-154: a nested torch.autograd.grad on a freshly flagged leaf -- LogisticRegression): capture refuses it."""
-    fns = list(score_fns)
-    inner = getattr(ctrl, "score", ctrl)  # RemoveReferenceCtrl wraps the score control
-    if hasattr(inner, "target_score"):
-        fns.append(inner.target_score)
-    return all(type(getattr(f, "__self__", None)).__name__ not in E._GRAPHLESS_SCORE for f in fns)
-
-
-def _graphed_step(loss, key, step, grads, example):
-    """``step`` captured as a hipGraph with static inputs / outputs (torch.cuda.graphs), cached on the loss per key; None if capture is not
-    possible (the caller then runs the step eagerly)."""
-    import weakref
-    cache = loss.__dict__.setdefault("_step_graphs", {})
-    ctrl_now = loss.generative_ctrl
-    hit = cache.get(key)
-    if hit is not None and hit is not False and hit.owner() is not ctrl_now:
-        hit = None  # (another control object at a recycled id: the captured graph reads the old one's parameters)
-    if hit is None:
-        try:
-            hit = _GraphedAdjointStep(step, grads, example)
-            hit.owner = weakref.ref(ctrl_now)
-        except Exception as e:  # noqa: BLE001 -- capture is an optimisation: run the steps eagerly, say so once
-            import warnings
-            warnings.warn(f"KL training: graph capture of the adjoint step failed ({type(e).__name__}: {e}); running it eagerly")
-            hit = False
-        cache[key] = hit
-    if hit is False:
-        return None
-    hit.reset()
-    return hit
-
-
-class _GraphedAdjointStep:
-    """One adjoint step (forward of the step's formulas + torch.autograd.grad) captured as a hipGraph.  The step function closes over
-    per-call tensors (the accumulators); the captured graph keeps its own static accumulators and inputs, refreshed per call."""
-
-    def __init__(self, step, grads, example):
-        self.static_in = [t.detach().clone() for t in example]
-        self.grads = [torch.zeros_like(g) for g in grads]
-        grads_backup = [g.clone() for g in grads]
-        self._swap(grads, self.grads)  # the closure accumulates into `grads`: make those our static buffers during warm-up / capture
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    step(*self.static_in)
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.static_out = step(*self.static_in)
-        finally:  # whatever happened, the caller's accumulators get their own storage and their values back
-            torch.cuda.synchronize()
-            self._unswap(grads, grads_backup)
-
-    def _swap(self, grads, mine):
-        self._held = [g.data for g in grads]
-        for g, m in zip(grads, mine):
-            g.data = m.data
-
-    def _unswap(self, grads, backup):
-        for g, h, b in zip(grads, self._held, backup):
-            g.data = h
-            g.copy_(b)
-
-    def reset(self):
-        for g in self.grads:
-            g.zero_()
-
-    def __call__(self, *inputs):
-        for s, i in zip(self.static_in, inputs):
-            s.copy_(i)
-        self.graph.replay()
-        return self.static_out
+        tdev = ts.to(x.device)  # (the ~130 small kernels of a step are launch-bound, 2048 x 100: 5 ms per step: walk_adjoint replays them as a hipGraph)
+        found = T.walk_adjoint(self, ("cmcd", id(ctrl), B, d, str(x.device)), step, grads, lam, lambda k: (xs[k], z[k], tdev[k], tdev[k + 1], w), N,
+                               self.graph_adjoint and _capturable(ctrl, self.sde.target_score))
+        return T.hand_to_autograd(self, value, params, found)
 
 
 class DiscreteTimeReversalLossEI(_InitialLogProbLoss):
@@ -1060,12 +709,12 @@ class DiscreteTimeReversalLossEI(_InitialLogProbLoss):
 
     def __call__(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None):
         """[TRAINING] losses/oc.py:1038-1066, log-variance methods (rnd0 = log p_prior(x0), terminal -log pi~)."""
-        def sim(xx, z):
+        def sim(xx):
             return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=None, train=True,
-                                 change_sde_ctrl=False, return_traj=True, use_ema=False, noise=z)
+                                 change_sde_ctrl=False, return_traj=True, use_ema=False)
         if self.method in ("kl", "kl_ito"):  # :1038-1066; rnd0 = 0 for the KL methods (:935-939)
-            return self._kl_loss(ts, x, lambda xx: sim(xx, None), lambda xn: -terminal_unnorm_log_prob(xn).view(-1, 1), lin=True)
-        return self._lv_loss(ts, x, sim, lambda xn: -self._logp(terminal_unnorm_log_prob, xn), lin=True, rnd0=initial_log_prob)
+            return self._kl_loss(ts, x, sim, lambda xn: -terminal_unnorm_log_prob(xn).view(-1, 1), lin=True)
+        return self._lv_loss(ts, x, sim, rnd0=initial_log_prob)
 
     def compute_eubo(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, use_ema=False, *, noise=None):
         """losses/oc.py:980-1036: noising trajectories from target samples (no reference; cost 0.5|u|^2 omega, Ito term,
@@ -1109,16 +758,15 @@ class TimeReversalLoss(_InitialLogProbLoss):
         kl = self.method in ("kl", "kl_ito")
         ito = self.method != "kl"  # :1251 compute_ito_int = self.method != "kl"
 
-        def sim(xx, z):
+        def sim(xx):
             return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=None, train=True,
-                                 compute_ito_int=ito, change_sde_ctrl=False, return_traj=True, use_ema=False, noise=z)
+                                 compute_ito_int=ito, change_sde_ctrl=False, return_traj=True, use_ema=False)
         if kl:
             if self.inference_ctrl is not None:
                 raise E.UnsupportedByEngine("a learned inference control needs the divergence of a net (autograd): not on the HIP path")
-            return self._kl_loss(ts, x, lambda xx: sim(xx, None), lambda xn: -terminal_unnorm_log_prob(xn).view(-1, 1), lin=False,
+            return self._kl_loss(ts, x, sim, lambda xn: -terminal_unnorm_log_prob(xn).view(-1, 1), lin=False,
                                  coef_kw=dict(train=True, dim=x.shape[-1], lerp=lerp), ito=ito)
-        return self._lv_loss(ts, x, sim, lambda xn: -self._logp(terminal_unnorm_log_prob, xn), lin=False, rnd0=initial_log_prob,
-                             coef_kw=dict(train=True, dim=x.shape[-1], lerp=lerp))
+        return self._lv_loss(ts, x, sim, rnd0=initial_log_prob, coef_kw=dict(train=True, dim=x.shape[-1], lerp=lerp))
 
 
 class ExponentialIntegratorSDELoss(BaseOCLoss):
@@ -1141,15 +789,14 @@ class ExponentialIntegratorSDELoss(BaseOCLoss):
         """[TRAINING] losses/oc.py:1399-1428, log-variance methods (compute_ito_int = True for them)."""
         ito = self.method != "kl"  # :1414 compute_ito_int = self.method != "kl"
 
-        def sim(xx, z):
+        def sim(xx):
             return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                                 compute_ito_int=ito, change_sde_ctrl=False, return_traj=True, use_ema=False, noise=z)
+                                 compute_ito_int=ito, change_sde_ctrl=False, return_traj=True, use_ema=False)
         if self.method in ("kl", "kl_ito"):
-            return self._kl_loss(ts, x, lambda xx: sim(xx, None),
+            return self._kl_loss(ts, x, sim,
                                  lambda xn: reference_log_prob(xn).view(-1, 1) - terminal_unnorm_log_prob(xn).view(-1, 1), lin=True,
                                  coef_kw=dict(alpha=self.alpha, sigma=self.sigma), ito=ito)
-        return self._lv_loss(ts, x, sim, lambda xn: self._logp(reference_log_prob, xn) - self._logp(terminal_unnorm_log_prob, xn), lin=True,
-                             coef_kw=dict(alpha=self.alpha, sigma=self.sigma))
+        return self._lv_loss(ts, x, sim, coef_kw=dict(alpha=self.alpha, sigma=self.sigma))
 
     def eval(self, ts, x, terminal_unnorm_log_prob, reference_log_prob=None, compute_weights=True, return_traj=True,
              use_ema=True, *, noise=None) -> Results:

@@ -295,11 +295,44 @@ def test_kl_training_native_adjoint_equals_the_stepwise_one(gpu):
         loss.seed = c.meta["seed"]
         value, _ = loss(b["ts"], b["x0"], *b["args"])
         value.backward()
+        assert loss.last_adjoint_path == ("native" if native else "fused")  # (a ClippedCtrl: its per-step form is one sdeng_ctrl_vjp per step)
         out[native] = (float(value.detach()), {k: p.grad.clone() for k, p in loss.generative_ctrl.named_parameters() if p.grad is not None})
     assert out[True][0] == out[False][0]
     worst = max(float((out[True][1][k] - g).abs().max() / g.abs().max().clamp(min=1e-30)) for k, g in out[False][1].items())
     print(f"native vs stepwise adjoint: worst relative gradient difference {worst:.2e}")
     assert worst < 1e-5
+
+
+@pytest.mark.gpu
+def test_the_three_kl_adjoints_run_and_agree(gpu):
+    """One fixture through each adjoint of BaseOCLoss._kl_loss -- the one-launch kernel, one sdeng_ctrl_vjp per step, one torch
+    vector-Jacobian product per step (a ClippedCtrl reaches the last only with fused_training off) -- from the fixture's seed: the call says
+    which one ran, the value (the same step-loop launch) is equal bit for bit, and every gradient set meets the bound
+    test_kl_training_loss_and_gradients_match_reference holds this fixture to against the reference's ``backward()``."""
+    c = gc.load("train_kl_ei_gmm_d16")
+    c.meta["kind"] = KINDS["train_lv"]
+    tol = max(5e-5, 10 * c.meta.get("grad_sensitivity", 0.0))
+    values = []
+    for native, fused, path in ((True, True, "native"), (False, True, "fused"), (False, False, "stepwise")):
+        b = bc.build(c, gpu)
+        loss = b["loss"]
+        loss.method, loss.max_rnd, loss.native_adjoint, loss.fused_training = "kl", None, native, fused
+        loss.seed = c.meta["seed"]
+        value, _ = loss(b["ts"], b["x0"], *b["args"])
+        value.backward()
+        assert loss.last_adjoint_path == path
+        values.append(float(value.detach()))
+        worst, n = 0.0, 0
+        for k, p in loss.generative_ctrl.named_parameters():
+            if "grad." + k not in c.a:
+                assert p.grad is None or float(p.grad.abs().max()) == 0.0, (path, k)
+                continue
+            ref = c["grad." + k]
+            worst, n = max(worst, float((p.grad.cpu() - ref).abs().max()) / max(float(ref.abs().max()), 1e-6)), n + 1
+        print(f"train_kl_ei_gmm_d16 through the {path} adjoint: worst relative gradient error {worst:.2e} over {n} parameters (tolerance {tol:.1e})")
+        assert n >= 8 and worst < tol, path
+    assert abs(values[0] - c.meta["loss"]) / max(1.0, abs(c.meta["loss"])) < 1e-5
+    assert values[0] == values[1] == values[2]
 
 
 @pytest.mark.gpu
@@ -328,6 +361,7 @@ def test_native_adjoint_equals_stepwise_for_every_control(gpu, solver, ref, inte
         model.setup_optim()
         loss, _ = model.compute_loss()
         loss.backward()
+        assert model.loss.last_adjoint_path == ("native" if native else ("fused" if ctrl_name == "ClippedCtrl" else "stepwise"))
         out[native] = (float(loss.detach()), {k: p.grad.clone() for k, p in ctrl.named_parameters() if p.grad is not None})
     assert out[True][0] == out[False][0] and out[True][1].keys() == out[False][1].keys()
     worst = max(float((out[True][1][k] - g).abs().max() / g.abs().max().clamp(min=1e-30)) for k, g in out[False][1].items())
@@ -354,6 +388,7 @@ def test_kl_training_at_baseline_config_1_size(gpu):
         model.setup_optim()
         loss, _ = model.compute_loss()
         loss.backward()
+        assert model.loss.last_adjoint_path == ("native" if native else "stepwise")
         grads[native] = (float(loss.detach()), {k: p.grad.clone() for k, p in model.generative_ctrl.named_parameters() if p.grad is not None})
     assert grads[True][0] == grads[False][0]
     worst = max(float((grads[True][1][k] - g).abs().max() / g.abs().max().clamp(min=1e-30)) for k, g in grads[False][1].items())
@@ -378,6 +413,7 @@ def test_native_adjoint_on_logistic_regression_targets(gpu, name):
         kw = {k: v for k, v in b["kwargs"].items() if k == "initial_log_prob"}
         value, _ = loss(b["ts"], b["x0"], *b["args"], **kw)
         value.backward()
+        assert loss.last_adjoint_path == ("native" if native else "stepwise")
         out[native] = (float(value.detach()), {k: p.grad.clone() for k, p in loss.generative_ctrl.named_parameters() if p.grad is not None})
     assert out[True][0] == out[False][0] and out[True][1].keys() == out[False][1].keys()
     worst = max(float((out[True][1][k] - g).abs().max() / g.abs().max().clamp(min=1e-30)) for k, g in out[False][1].items())
