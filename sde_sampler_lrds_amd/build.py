@@ -59,10 +59,12 @@ def _cmcd(nt):
 # SC (in-loop score of a Score / Lerp / CancelDrift control): 0 none, 1 mixture / rings, 2 phi^4, 3 logistic regression, 4 the
 # full-covariance target held in the reference slot.
 UNITS = {
-    **{f"sim_{nt}_{ref}_{sc}": _sim(nt, ref, sc, (LIN, EM) + ((EUBO,) if (sc == 0) != (ref == 0) else ()))
+    # (EUBO: every reference-SDE loss -- ClippedCtrl or a score control --, and DIS without a reference)
+    **{f"sim_{nt}_{ref}_{sc}": _sim(nt, ref, sc, (LIN, EM) + ((EUBO,) if ref != 0 or sc != 0 else ()))
        for nt in DTS for ref in (0, 1, 2, 3) for sc in (0, 1, 2)},
     **{f"sim_{nt}_0_3": _sim(nt, 0, 3, (LIN, EM)) for nt in (1, 2, 3, 4)},  # logistic-regression design matrix in LDS: d <= 64
     **{f"sim_{nt}_4_0": _sim(nt, 4, 0, (LIN, EM, EUBO)) for nt in DTS_FULL},
+    **{f"sim_{nt}_4_{sc}": _sim(nt, 4, sc, (LIN, EM, EUBO)) for nt in DTS_FULL for sc in (1, 2)},  # score control over a full-covariance reference
     **{f"sim_{nt}_4_4": _sim(nt, 4, 4, (LIN, EM)) for nt in DTS_FULL},
     **{f"sim_{nt}_5_0": _sim(nt, 5, 0, (LIN, EM)) for nt in DTS},
     **{f"ctrl_{nt}": [("ctrl", nt, (sc,)) for sc in (0, 1, 2)] for nt in DTS},

@@ -478,22 +478,23 @@ static int plan_sim(SimPlan& p) {
   if (init_logp && !eubo && d->prior.kind == SDENG_DIST_NONE) return fail(SDENG_E_INVALID, "FLAG_INIT_LOGP without a prior");
   if ((d->flags & SDENG_FLAG_TERM_REF) && d->ref_dist.kind == SDENG_DIST_NONE) return fail(SDENG_E_INVALID, "FLAG_TERM_REF without ref_dist");
   if ((d->flags & SDENG_FLAG_TERM_TARGET) && d->target.kind == SDENG_DIST_NONE) return fail(SDENG_E_INVALID, "FLAG_TERM_TARGET without target");
-  if ((d->flags & SDENG_FLAG_REMOVE_REF) && (sc == SC_NONE || sc == SC_LOGREG || rf == RF_NONE || rf == RF_GMM_FULL || rf == RF_GMM_MM || eubo))
+  if ((d->flags & SDENG_FLAG_REMOVE_REF) && (sc == SC_NONE || sc == SC_LOGREG || sc == SC_REFSLOT || rf == RF_NONE || rf == RF_GMM_MM || eubo))
     return fail(SDENG_E_UNSUPPORTED, "FLAG_REMOVE_REF (RemoveReferenceCtrl): forward forms with a Score / Lerp / CancelDrift control on a mixture or "
-                                     "phi^4 target and a diagonal Gaussian / mixture reference (ctrl_kind %d, ref.kind %d, form %d)",
+                                     "phi^4 target and a Gaussian / mixture reference (ctrl_kind %d, ref.kind %d, form %d)",
                 d->net.ctrl_kind, d->ref.kind, d->form);
   if (eubo) {
-    if ((rf == RF_NONE) == (sc == SC_NONE))
-      return fail(SDENG_E_UNSUPPORTED, "compute_eubo kernels: a reference drift with a ClippedCtrl, or no reference with a Score/LerpCtrl "
+    if (rf == RF_NONE && sc == SC_NONE)
+      return fail(SDENG_E_UNSUPPORTED, "compute_eubo kernels: a reference drift, or no reference with a Score/LerpCtrl "
                                        "(ref.kind %d, ctrl_kind %d)", d->ref.kind, d->net.ctrl_kind);
     if (sc == SC_LOGREG) return fail(SDENG_E_UNSUPPORTED, "compute_eubo kernels: no logistic-regression control score");
     if (init_logp && d->prior.kind == SDENG_DIST_NONE) return fail(SDENG_E_INVALID, "FLAG_INIT_LOGP without a prior");
   } else if (sc == SC_LOGREG) {  // ScoreCtrl / LerpCtrl on a logistic-regression target (PIS, DDS, DIS on the Bayesian benchmarks)
     if (rf != RF_NONE) return fail(SDENG_E_UNSUPPORTED, "in-loop logistic-regression score together with a reference drift");
     if (DT > 4) return fail(SDENG_E_UNSUPPORTED, "in-loop logistic-regression score: d <= 64 (got %d)", d->d);
-  } else if (rf == RF_GMM_FULL && sc != SC_NONE && sc != SC_REFSLOT) {
-    return fail(SDENG_E_UNSUPPORTED, "full-covariance reference together with a Score/LerpCtrl");
   }
+  // defensive: use_mm keeps score controls and the noising form on the vector path, so no such instance is ever asked for
+  if (rf == RF_GMM_MM && (sc != SC_NONE || eubo))
+    return fail(SDENG_E_UNSUPPORTED, "matrix-pipe mixture reference: forward forms with a ClippedCtrl only");
   const bool pert = d->flags & (SDENG_FLAG_CTRL_NOISE | SDENG_FLAG_CTRL_DROPOUT);  // (forward forms only: plan_simulate checks)
   if (split_eligible(d, DT) && (rf == RF_NONE || rf == RF_GAUSS || rf == RF_GMM)) return select_kernel(p.k, SD_FAM_SPLIT, DT, rf, d->form, pert);
   return select_kernel(p.k, SD_FAM_SIM, DT, rf, sc, d->form, pert ? 2 : (d->noise_in || d->xs_out) ? 1 : 0);

@@ -45,7 +45,7 @@ SD_INLINE int feat(int t, int r, int g) { return 16 * t + 4 * g + r; }
 SD_INLINE bool feat_lt(int t, int r, int g4, int d) { return g4 < d - (16 * t + r); }
 // The same for a kernel with NT feature tiles: NT = ceil(d / 16) exactly (sdeng_api.hip tiles_of), so every tile but the last
 // holds live features only -- no mask instructions there (t is a compile-time constant after unrolling).  (The full-covariance
-// reference kernels may run with one tile more than that; they never use this helper.)
+// reference kernels may run with one tile more than that; they never use this helper: feat_lt in every tile.)
 template <int NT>
 SD_INLINE bool feat_live(int t, int r, int g4, int d) { return (t < NT - 1) ? true : feat_lt(t, r, g4, d); }
 
@@ -891,7 +891,10 @@ SD_INLINE void phi4_edges(const f32x4 (&x)[NT], int t, int g, int lane, float& l
 }
 
 // PhiFour.score = -beta * grad_U  (distr/phi_four.py:81-96); p0=a, p1=b, p2=beta
-template <int NT>
+// EXACT: NT = ceil(d / 16), feat_live's premise.  The step loop over a full-covariance reference may run with a tile more (sdeng_api.hip
+// tiles_of): there pad features are masked by the run-time d in every tile, and so is the right neighbour of the last live site --
+// whatever the pad features of x hold, it never reaches a live one through the lattice term.
+template <int NT, bool EXACT = true>
 SD_INLINE void phi4_score(const f32x4 (&x)[NT], const DistDev& ds, int d, int g, int lane, f32x4 (&acc)[NT]) {
   const float coef = ds.p0 * static_cast<float>(d);
   // -beta * [ (b - x (1 - x^2)) / coef + coef (2 x - x_r - x_l) ]  =  A (x^3 - x) + K0 + C (2 x - x_r - x_l)
@@ -907,11 +910,12 @@ SD_INLINE void phi4_score(const f32x4 (&x)[NT], const DistDev& ds, int d, int g,
     for (int r = 0; r < 4; ++r) {
       const float xv = x[t][r];
       const float xl = (r == 0) ? le : x[t][r > 0 ? r - 1 : 0];
-      const float xr = (r == 3) ? re : x[t][r < 3 ? r + 1 : 3];
+      float xr = (r == 3) ? re : x[t][r < 3 ? r + 1 : 3];
+      if constexpr (!EXACT) xr = feat_lt(t, r + 1, 4 * g, d) ? xr : 0.0f;
       const float cub = __builtin_fmaf(xv * xv, xv, -xv);                      // x^3 - x
       const float lap = __builtin_fmaf(2.0f, xv, -xr) - xl;                     // 2 x - x_r - x_l
       const float sc = __builtin_fmaf(C, lap, __builtin_fmaf(A, cub, K0));
-      acc[t][r] = feat_live<NT>(t, r, 4 * g, d) ? sc : 0.0f;
+      acc[t][r] = (EXACT ? feat_live<NT>(t, r, 4 * g, d) : feat_lt(t, r, 4 * g, d)) ? sc : 0.0f;
     }
   }
 }

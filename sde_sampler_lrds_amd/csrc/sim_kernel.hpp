@@ -200,7 +200,11 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
   const int p = lane & 15, g = lane >> 4;
   constexpr bool lin = FORM == SDENG_FORM_LIN;
   constexpr bool eubo = FORM == SDENG_FORM_EUBO;  // noising direction (compute_eubo)
-  static_assert(!eubo || (SC == SC_NONE) != (REF == RF_NONE), "EUBO kernels: reference-SDE losses with a ClippedCtrl, or DIS (no reference)");
+  static_assert(!eubo || (SC == SC_NONE) != (REF == RF_NONE) || ((SC == SC_GMM || SC == SC_PHI4) && REF >= RF_GAUSS && REF <= RF_GMM_FULL),
+                "EUBO kernels: reference-SDE losses (ClippedCtrl, or a score control on a mixture / phi^4 target), or DIS (no reference)");
+  // NT = ceil(d / 16) exactly, except over a full-covariance reference (5 and 7 tiles run on the 6- and 8-tile instances): there the
+  // pad masks of the phi^4 noise / score and of the control perturbation take the run-time d in every tile
+  constexpr bool exact_nt = REF != RF_GMM_FULL;
   const bool full_d = a.d == dpad;
   float* trash = a.trash + tid * 4;
   bool same_var = false;
@@ -258,7 +262,7 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
         if constexpr (SC == SC_PHI4) {
           if (!full_d) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) z[r] = feat_live<NT>(t, r, 4 * g, d_dyn) ? z[r] : 0.0f;
+            for (int r = 0; r < 4; ++r) z[r] = (exact_nt ? feat_live<NT>(t, r, 4 * g, d_dyn) : feat_lt(t, r, 4 * g, d_dyn)) ? z[r] : 0.0f;
           }
         }
         return z;
@@ -298,11 +302,13 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
 
       // ---- scores at the OLD state: target score inside the control, reference drift ----
       f32x4 ts[(SC != SC_NONE && SC != SC_REFSLOT) ? NT : 1];
-      if constexpr (SC == SC_GMM) {
+      // (over a full-covariance reference the target score is formed AFTER the reference block below: ts[NT] is then not live across
+      // the per-component loop, whose matrix products need the registers)
+      if constexpr (SC == SC_GMM && exact_nt) {
         if (NT == 1 && a.target.kind == SDENG_DIST_RINGS) ts[0] = rings_score(x[0], a.target, g);
         else gmm_score<NT>(x, a.target.tab, a.target.consts, 4, a.target.k, a.target.p0, g, ts);
       }
-      if constexpr (SC == SC_PHI4) {
+      if constexpr (SC == SC_PHI4 && exact_nt) {
         // (eight feature tiles at three waves per SIMD: the neighbour-lane indices of the lattice score, left loop-invariant, are parked in
         // scratch and reloaded every step; derived from an opaque copy of the lane id they are two integer instructions next to their use)
         int lane_p = lane;
@@ -512,6 +518,15 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
             for (int r = 0; r < 4; ++r) rs[t][r] = __builtin_fmaf(pk, v[t][r], rs[t][r] * so);
         }
         gmm_score_end<NT>(rs, l_run);
+        if constexpr (SC == SC_GMM) {
+          if (NT == 1 && a.target.kind == SDENG_DIST_RINGS) ts[0] = rings_score(x[0], a.target, g);
+          else gmm_score<NT>(x, a.target.tab, a.target.consts, 4, a.target.k, a.target.p0, g, ts);
+        }
+        if constexpr (SC == SC_PHI4) {
+          int lane_p = lane;  // (as above: neighbour-lane indices re-derived next to their use instead of parked in scratch)
+          if constexpr (NT == 8) asm volatile("" : "+v"(lane_p));
+          phi4_score<NT, false>(x, a.target, d_dyn, g, lane_p, ts);
+        }
       }
       float st = 1.0f;
       if constexpr (SC != SC_NONE) st = a.stheta ? a.stheta[k] : 1.0f;
@@ -601,7 +616,7 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
             rq = ref_tile(t);
             if (a.flags & SDENG_FLAG_REMOVE_REF) u[o] = u[o] - rq;
           }
-          if constexpr (PAR == 2) perturb_ctrl_tile<NT, REF != RF_GMM_FULL>(a, cf, u[o], x[t], pidx, k, t, g, d_dyn);  // everything below consumes the perturbed control
+          if constexpr (PAR == 2) perturb_ctrl_tile<NT, exact_nt>(a, cf, u[o], x[t], pidx, k, t, g, d_dyn);  // everything below consumes the perturbed control
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float uv = u[o][r];

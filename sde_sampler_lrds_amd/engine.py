@@ -613,7 +613,10 @@ def run(desc: L.Desc, x: torch.Tensor, keep: list, return_traj=False, noise=None
     desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
     if events is not None:
         desc.ev_start, desc.ev_stop = events.start, events.stop
-    L.check(lib.sdeng_simulate(C.byref(desc), _stream_ptr(device)))
+    rc = lib.sdeng_simulate(C.byref(desc), _stream_ptr(device))
+    if rc == L.E_UNSUPPORTED:  # a combination the library has no kernel for (INTEGRATION.md "Limits, first"): the documented exception, its reason
+        raise UnsupportedByEngine(lib.sdeng_last_error().decode())
+    L.check(rc)
     return x_out, rnd, xs
 
 
