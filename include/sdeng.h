@@ -107,7 +107,7 @@ extern "C" {
  *   CTRL_DROPOUT  then u = -(coef[14] * x) / coef[15] wherever U > coef[13] (x: the state of the step), U = output word feature % 4 of
  *                 Philox4x32-10 with counter (particle0+p, feature/4, step, 5), as ((bits>>9)+0.5)*2^-23.  `U > p` is the reference's
  *                 convention (`rand_like > sde_ctrl_dropout`): an element is REPLACED with probability 1 - p.
- * (Streams 2 and 3 belong to sdeng_langevin_moves.)  FORM_LIN / FORM_EM with a drift net; SDENG_E_UNSUPPORTED otherwise (CMCD, EUBO, Euler). */
+ * (Streams 2 and 3 belong to sdeng_langevin_moves, 6 and 7 to sdeng_rwmh_moves: 0-7 are taken.)  FORM_LIN / FORM_EM with a drift net; SDENG_E_UNSUPPORTED otherwise (CMCD, EUBO, Euler). */
 #define SDENG_FLAG_CTRL_NOISE 128u
 #define SDENG_FLAG_CTRL_DROPOUT 256u
 
@@ -398,6 +398,22 @@ int sdeng_langevin_moves(const sdeng_dist* prior, const sdeng_dist* target, int3
                          const float* z, const float* u, uint64_t seed, int64_t chain0, float* samples, float* acc_sum, float* acc_last,
                          void* workspace, size_t workspace_bytes, void* stream);
 size_t sdeng_langevin_moves_workspace_bytes(const sdeng_dist* prior, const sdeng_dist* target, int32_t d);
+
+/* Learned-reference data set: n_moves random-walk Metropolis moves of B chains in ONE launch -- rwmh_step of additions/mcmc.py:256-293 with
+ * the per-chain step-size heuristic of :54-72 (target_acceptance > 0), as mcmc_sample(mcmc_type='rwmh') applies them move after move
+ * (experiments/benchmark_utils.py:299-327; the checkerboard's data set, experiments/sample_toy_gmm_mcmc.py:112-115).  Proposal
+ * x + step[b] * z (the standard deviation is the step itself), log_acc = log pi~(prop) - lp[b], accepted iff log(u) < log_acc.  Every
+ * distribution kind sdeng_dist_eval has a log-density for, SDENG_DIST_CHECKERBOARD included: non-finite log-densities keep their IEEE
+ * meaning (-inf: rejected, the step shrinks; +inf from a start outside every square: accepted, the step grows; NaN: rejected, the step
+ * stays).  No tempering (the reference has no tempered random-walk move).  State in / out: x [B,d], lp [B] = log pi~(x), step [B].
+ * Noise: injected normals z [n_moves,B,d] and uniforms u [n_moves,B], both or neither; NULL: Philox stream 6 for the normals (the
+ * counter layout of the step noise, keyed by (seed, chain0 + chain, move): sdeng_philox_normal_steps(..., stream_id = 6) replays them)
+ * and stream 7 for the uniforms (counter (chain0 + chain, 0, move, 7), output word 0).  samples / acc_sum / acc_last: as
+ * sdeng_langevin_moves.  d <= 255 (SDENG_E_UNSUPPORTED above); keep_from <= n_moves. */
+int sdeng_rwmh_moves(const sdeng_dist* target, int32_t B, int32_t d, int32_t n_moves, int32_t keep_from, float target_acceptance,
+                     float* x, float* lp, float* step, const float* z, const float* u, uint64_t seed, int64_t chain0,
+                     float* samples, float* acc_sum, float* acc_last, void* workspace, size_t workspace_bytes, void* stream);
+size_t sdeng_rwmh_moves_workspace_bytes(const sdeng_dist* target, int32_t d);
 
 /* prior.sample((B,)) on the device, out[B,d]: exactly the x0 that sdeng_simulate draws for x_in == NULL with the same
  * (dist, seed, particle0).  Replaces IsotropicGauss.sample / Gauss.sample / Delta.sample / GaussFull.sample (distr/gauss.py:772-787,

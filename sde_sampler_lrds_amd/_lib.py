@@ -86,7 +86,7 @@ EXPORTS = ["sdeng_abi_version", "sdeng_last_error", "sdeng_workspace_bytes", "sd
            "sdeng_philox_normal", "sdeng_philox_normal_steps", "sdeng_sample_x0", "sdeng_ctrl_vjp", "sdeng_ctrl_vjp_workspace_bytes",
            "sdeng_langevin_moves", "sdeng_langevin_moves_workspace_bytes", "sdeng_kl_adjoint", "sdeng_kl_adjoint_workspace_bytes",
            "sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes",
-           "sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes"]
+           "sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes", "sdeng_rwmh_moves", "sdeng_rwmh_moves_workspace_bytes"]
 
 
 def lib() -> C.CDLL:
@@ -138,6 +138,11 @@ def lib() -> C.CDLL:
         [C.c_void_p] * 7 + [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.sdeng_langevin_moves_workspace_bytes.restype = C.c_size_t
     L.sdeng_langevin_moves_workspace_bytes.argtypes = [C.POINTER(Dist), C.POINTER(Dist), C.c_int32]
+    L.sdeng_rwmh_moves.restype = C.c_int
+    L.sdeng_rwmh_moves.argtypes = [C.POINTER(Dist), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + \
+        [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sdeng_rwmh_moves_workspace_bytes.restype = C.c_size_t
+    L.sdeng_rwmh_moves_workspace_bytes.argtypes = [C.POINTER(Dist), C.c_int32]
     L.sdeng_sinkhorn.restype = C.c_int
     L.sdeng_sinkhorn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double] + \
         [C.c_void_p] * 6 + [C.POINTER(SinkhornResult), C.c_void_p, C.c_size_t, C.c_void_p]

@@ -49,6 +49,14 @@ def _native_run(pair, t, x, lp, grad, step, n_moves, keep_from, use_ula, target_
                             seed=(NATIVE_SEED + 0x9E3779B97F4A7C15 * _native_calls[0]) & 0xFFFFFFFFFFFFFFFF, want_samples=want_samples)
 
 
+def _native_rwmh(target, x, lp, step, n_moves, keep_from, target_acceptance):
+    """n_moves random-walk Metropolis moves of all chains (csrc/prep_kernels.hip k_rwmh_moves); x / lp / step ([B,d], [B], [B] contiguous) are
+    updated in place.  Random numbers as configured above, like the Langevin moves."""
+    _native_calls[0] += 1
+    return E.rwmh_moves(target, x, lp, step, n_moves, keep_from=keep_from, target_acceptance=target_acceptance,
+                        noise="philox" if NATIVE_NOISE else "torch", seed=(NATIVE_SEED + 0x9E3779B97F4A7C15 * _native_calls[0]) & 0xFFFFFFFFFFFFFFFF)
+
+
 def _pmul(mat, v):
     return torch.matmul(mat, v.unsqueeze(-1)).squeeze(-1)
 

@@ -857,6 +857,68 @@ __global__ void __launch_bounds__(64) k_langevin_moves(MovesArgs a, int chains_p
   if (a.acc_last) a.acc_last[chain] = last;
 }
 
+// Random-walk Metropolis moves of the learned-reference data set (experiments/benchmark_utils.py:281-290 -> rwmh_step, additions/mcmc.py:
+// 256-293, with heuristics_step_size of :54-72): the layout of k_langevin_moves -- one thread per chain, no barriers -- with two LDS rows per
+// chain (state, proposal), no gradient and no score call.  Non-finite log-densities keep their IEEE meaning, which is the reference's on the
+// checkerboard: a proposal outside every square has log_acc = -inf (rejected, the step shrinks); a chain that starts outside (lp = -inf)
+// has +inf for a proposal inside (accepted, the step grows) and NaN for one outside (rejected, both step comparisons are false).
+#define SD_RWMH_ROWS 2  // x, proposal
+__global__ void __launch_bounds__(64) k_rwmh_moves(RwmhArgs a, int chains_per_block) {
+  extern __shared__ float sh[];
+  const int tid = threadIdx.x, d = a.d, stride = d | 1;
+  const int chain = blockIdx.x * chains_per_block + tid;
+  if (tid >= chains_per_block || chain >= a.B) return;  // (no barriers below: a chain is one thread)
+  float* xr = sh + (tid * SD_RWMH_ROWS + 0) * stride;
+  float* pr = xr + stride;
+  for (int f = 0; f < d; ++f) xr[f] = a.x[static_cast<size_t>(chain) * d + f];
+  float lp = a.lp[chain], step = a.step[chain], acc = 0.0f, last = 1.0f;
+  const uint32_t cidx = static_cast<uint32_t>(a.chain0 + chain);
+  const float log_target = a.target_acc > 0.0f ? logf(a.target_acc) : 0.0f;
+  for (int m = 0; m < a.K; ++m) {
+    // proposal: y + step_size * randn_like(y) -- the standard deviation is the step itself (mcmc.py:279)
+    for (int f0 = 0; f0 < d; f0 += 4) {
+      f32x4 z;
+      if (a.z) {
+        for (int r = 0; r < 4; ++r) z[r] = f0 + r < d ? a.z[(static_cast<size_t>(m) * a.B + chain) * d + f0 + r] : 0.0f;
+      } else {
+        z = philox_normal4(cidx, static_cast<uint32_t>(m), static_cast<uint32_t>(f0 >> 2), 6u, a.seed_lo, a.seed_hi);
+      }
+      for (int r = 0; r < 4 && f0 + r < d; ++r) pr[f0 + r] = xr[f0 + r] + step * z[r];
+    }
+    const float lp_p = dist_logp_row(a.target, pr);
+    const float log_acc = lp_p - lp;  // (mcmc.py:283)
+    float uu;
+    if (a.u) {
+      uu = a.u[static_cast<size_t>(m) * a.B + chain];
+    } else {
+      uint32_t r4[4];
+      philox4x32_10(cidx, 0u, static_cast<uint32_t>(m), 7u, a.seed_lo, a.seed_hi, r4);
+      uu = u01(r4[0]);
+    }
+    if (logf(uu) < log_acc) {
+      for (int f = 0; f < d; ++f) xr[f] = pr[f];
+      lp = lp_p;
+    }
+    if (a.target_acc > 0.0f) {  // heuristics_step_size (mcmc.py:54-72), per chain
+      if (log_acc - log_target > 0.04879016416943205f) step = step * 1.01f;        // log1p(0.05)
+      if (log_target - log_acc > 0.05129329438755058f) step = step / 1.01f;        // -log1p(-0.05)
+    }
+    last = expf(fminf(0.0f, log_acc));
+    if (m >= a.keep_from) {
+      acc += last;
+      if (a.samples) {
+        float* dst = a.samples + (static_cast<size_t>(m - a.keep_from) * a.B + chain) * d;
+        for (int f = 0; f < d; ++f) dst[f] = xr[f];
+      }
+    }
+  }
+  for (int f = 0; f < d; ++f) a.x[static_cast<size_t>(chain) * d + f] = xr[f];
+  a.lp[chain] = lp;
+  a.step[chain] = step;
+  if (a.acc_sum) a.acc_sum[chain] = acc;
+  if (a.acc_last) a.acc_last[chain] = last;
+}
+
 // terminal cost, in place on rnd (losses/oc.py:290: rnd += ref_logp(x) - target_logp(x); :973: rnd -= target_logp(x))
 __global__ void __launch_bounds__(SD_EVAL_THREADS) k_terminal(TerminalArgs a) {
   extern __shared__ float sh[];
@@ -1080,6 +1142,10 @@ int sd_launch_moves(const MovesArgs& a, hipStream_t s) {
   while (cpb > 8 && static_cast<size_t>(cpb) * SD_MOVE_ROWS * stride * sizeof(float) > 150 * 1024) cpb /= 2;  // d > ~115: 32 chains per block
   const size_t lds = static_cast<size_t>(cpb) * SD_MOVE_ROWS * stride * sizeof(float);
   return sd_launch_kernel(k_langevin_moves, (a.B + cpb - 1) / cpb, 64, lds, s, a, cpb);
+}
+int sd_launch_rwmh(const RwmhArgs& a, hipStream_t s) {
+  const size_t lds = static_cast<size_t>(64) * SD_RWMH_ROWS * (a.d | 1) * sizeof(float);  // d <= 255: at most 128 KiB
+  return sd_launch_kernel(k_rwmh_moves, (a.B + 63) / 64, 64, lds, s, a, 64);
 }
 int sd_launch_terminal(const TerminalArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_terminal, dim3((a.B + SD_EVAL_ROWS - 1) / SD_EVAL_ROWS), dim3(SD_EVAL_THREADS), (SD_EVAL_ROWS * (a.d | 1) + SD_EVAL_RED_FLOATS) * sizeof(float), s, a);

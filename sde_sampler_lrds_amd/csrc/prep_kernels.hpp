@@ -91,6 +91,22 @@ struct MovesArgs {
 };
 int sd_launch_moves(const MovesArgs& a, hipStream_t s);
 
+// K random-walk Metropolis moves of B chains on the target alone, state in LDS: additions/mcmc.py:256-293 (rwmh_step) with the step-size
+// heuristic of :54-72, as mcmc_sample(mcmc_type='rwmh') applies them (experiments/benchmark_utils.py:299-327)
+struct RwmhArgs {
+  DistEvalArgs target;          // .ds / .d / .dpad
+  int B, d, K, keep_from;       // chains, dimension, moves, first stored move
+  float target_acc;             // <= 0: step sizes stay fixed
+  float *x, *lp, *step;         // [B,d], [B], [B]: chain state, carried in and out
+  const float *z, *u;           // injected normals [K,B,d] and uniforms [K,B], or nullptr: counter-based Philox draws (streams 6 / 7)
+  unsigned seed_lo, seed_hi;
+  long long chain0;             // global index of chain 0 (Philox counter)
+  float* samples;               // [K - keep_from, B, d] states after each stored move, or nullptr
+  float* acc_sum;               // [B] sum over the stored moves of min(1, acceptance ratio), or nullptr
+  float* acc_last;              // [B] min(1, acceptance ratio) of the last move, or nullptr
+};
+int sd_launch_rwmh(const RwmhArgs& a, hipStream_t s);
+
 struct TerminalArgs {
   DistDev ref, target;
   int use_ref, use_target;

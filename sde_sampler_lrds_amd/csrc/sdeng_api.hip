@@ -1055,6 +1055,37 @@ extern "C" int sdeng_langevin_moves(const sdeng_dist* prior, const sdeng_dist* t
   return 0;
 }
 
+// ---- random-walk Metropolis moves of the learned-reference data set (experiments/benchmark_utils.py:281-290) ------------------------
+extern "C" size_t sdeng_rwmh_moves_workspace_bytes(const sdeng_dist* target, int32_t d) {
+  if (!target || d < 1) return 0;
+  return (dist_floats(*target, pad16(d)) + 64) * sizeof(float);
+}
+extern "C" int sdeng_rwmh_moves(const sdeng_dist* target, int32_t B, int32_t d, int32_t n_moves, int32_t keep_from, float target_acceptance,
+                                float* x, float* lp, float* step, const float* z, const float* u, uint64_t seed, int64_t chain0,
+                                float* samples, float* acc_sum, float* acc_last, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!target || !x || !lp || !step || B < 0 || d < 1 || n_moves < 0 || keep_from < 0 || keep_from > n_moves) return fail(SDENG_E_INVALID, "bad argument");
+  if (d > 255) return fail(SDENG_E_UNSUPPORTED, "rwmh_moves: d <= 255 (chain rows live in LDS), got %d", d);
+  if ((z == nullptr) != (u == nullptr)) return fail(SDENG_E_INVALID, "rwmh_moves: inject both the normals and the uniforms, or neither");
+  if (target->kind == SDENG_DIST_NONE) return fail(SDENG_E_INVALID, "rwmh_moves: no target distribution");
+  SD_TRY(check_dist(*target, d));
+  if (B == 0 || n_moves == 0) return 0;
+  const int dpad = pad16(d);
+  const size_t need = sdeng_rwmh_moves_workspace_bytes(target, d);
+  if (!workspace || workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", workspace_bytes, need);
+  RwmhArgs a;
+  memset(&a, 0, sizeof(a));
+  SD_TRY(build_dist(*target, d, dpad, static_cast<float*>(workspace), a.target.ds, s));
+  a.target.d = d; a.target.dpad = dpad; a.target.B = B;
+  a.B = B; a.d = d; a.K = n_moves; a.keep_from = keep_from; a.target_acc = target_acceptance;
+  a.x = x; a.lp = lp; a.step = step; a.z = z; a.u = u;
+  const Seed sd = split_seed(seed);
+  a.seed_lo = sd.lo; a.seed_hi = sd.hi; a.chain0 = chain0;
+  a.samples = samples; a.acc_sum = acc_sum; a.acc_last = acc_last;
+  SD_HIP(sd_launch_rwmh(a, s));
+  return 0;
+}
+
 extern "C" size_t sdeng_dist_workspace_bytes(const sdeng_dist* dist, int32_t d) {
   if (!dist || d < 1) return 0;
   return dist_floats(*dist, pad16(d)) * sizeof(float);

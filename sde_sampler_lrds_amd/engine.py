@@ -799,6 +799,47 @@ def langevin_moves(target, prior, x, lp, grad, step, n_moves, *, t=None, keep_fr
     return samples, acc, last
 
 
+def rwmh_moves(target, x, lp, step, n_moves, *, keep_from=0, target_acceptance=0.0, noise="torch", seed=0, chain0=0, want_samples=True):
+    """sdeng_rwmh_moves: ``n_moves`` random-walk Metropolis moves of all chains in one launch (include/sdeng.h).  ``x`` [B,d], ``lp`` [B],
+    ``step`` [B] are updated IN PLACE.  ``noise='torch'``: per move ``torch.randn((B, d))`` then ``torch.rand((B,))`` on the device, the order
+    additions/mcmc.py:rwmh_step consumes them; ``noise='philox'``: drawn in the kernel (streams 6 / 7).  Everything the kernel indexes is
+    checked here.  Returns (samples [n_moves - keep_from, B, d] or None, acc_sum [B], acc_last [B])."""
+    require_gpu(x)
+    if x.dim() != 2:
+        raise ValueError(f"rwmh_moves: x must be [B, d], got {tuple(x.shape)}")
+    B, d = x.shape
+    n_moves, keep_from = int(n_moves), int(keep_from)
+    if lp.numel() != B or step.numel() != B:
+        raise ValueError(f"rwmh_moves: lp and step must hold one value per chain (B = {B}), got {lp.numel()} and {step.numel()}")
+    if not 0 <= keep_from <= n_moves:
+        raise ValueError(f"rwmh_moves: 0 <= keep_from <= n_moves, got keep_from = {keep_from}, n_moves = {n_moves}")
+    if noise not in ("torch", "philox"):
+        raise ValueError("noise: 'torch' or 'philox'")
+    for ok in (lambda v: v.dtype == torch.float32 and v.is_contiguous(), lambda v: v.is_cuda):
+        for name, v in (("x", x), ("lp", lp), ("step", step)):
+            if not ok(v):
+                raise ValueError(f"rwmh_moves: {name} must be a contiguous float32 CUDA tensor (it is updated in place)")
+    lib = L.lib()
+    device, keep = x.device, []
+    dt = dist_desc(target, device, keep)
+    z = u = None
+    if noise == "torch":
+        z = torch.empty(n_moves, B, d, dtype=torch.float32, device=device)
+        u = torch.empty(n_moves, B, dtype=torch.float32, device=device)
+        for m in range(n_moves):  # the reference's consumption order: one randn per proposal, then one rand per accept test
+            z[m] = torch.randn((B, d), device=device)
+            u[m] = torch.rand((B,), device=device)
+    samples = torch.empty(n_moves - keep_from, B, d, dtype=torch.float32, device=device) if want_samples else None
+    acc = torch.zeros(B, dtype=torch.float32, device=device)
+    last = torch.ones(B, dtype=torch.float32, device=device)
+    ws = torch.empty(max(lib.sdeng_rwmh_moves_workspace_bytes(C.byref(dt), d), 16), dtype=torch.uint8, device=device)
+    ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+    L.check(lib.sdeng_rwmh_moves(C.byref(dt), B, d, n_moves, keep_from, float(target_acceptance), x.data_ptr(), lp.data_ptr(), step.data_ptr(),
+                                 ptr(z), ptr(u), int(seed), int(chain0), ptr(samples), acc.data_ptr(), last.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _stream_ptr(device)))
+    return samples, acc, last
+
+
 def _net_only_desc(ctrl, t_unique: torch.Tensor, n_times: int, d: int, device, keep: list, who="ctrl_vjp", own_workspace=False):
     """The descriptor sdeng_ctrl_vjp reads -- the drift net of a ClippedCtrl, a coefficient table that holds only the ``n_times`` times (column 0),
     the shared workspace or one of its ``own`` (its weight images then survive other engine calls) -> (desc, coef, workspace), for the caller to keep alive."""

@@ -278,6 +278,13 @@ def mcmc_sample(device, target, x_init, mcmc_type="mala", step_size=1e-3, n_chai
                                         n_warmup_steps, False, 0.75 if adapt_step_size else 0.0)
         ret = got.cpu().view((-1, *x_init.shape[1:]))
         return ret[torch.randperm(ret.shape[0])] if shuffle else ret
+    if mcmc_type != "mala" and hip_target is not None and ebm_mle.NATIVE_MOVES and y.is_cuda and y.dim() == 2 and y.dtype == torch.float32:
+        # random-walk Metropolis (the only sampler of the checkerboard's data set): the same, k_rwmh_moves -- no score, two LDS rows per chain
+        y, lp = y.contiguous().clone(), lp.contiguous().float().clone()
+        got, _, _ = ebm_mle._native_rwmh(hip_target, y, lp, step.reshape(-1).contiguous().clone(), n_warmup_steps + n_mcmc_steps, n_warmup_steps,
+                                         0.75 if adapt_step_size else 0.0)
+        ret = got.cpu().view((-1, *x_init.shape[1:]))
+        return ret[torch.randperm(ret.shape[0])] if shuffle else ret
     ys = torch.empty((n_mcmc_steps, *y.shape))
     for step_id in range(n_warmup_steps + n_mcmc_steps):
         if mcmc_type == "mala":
@@ -291,3 +298,96 @@ def mcmc_sample(device, target, x_init, mcmc_type="mala", step_size=1e-3, n_chai
     ret = ys.view((-1, *x_init.shape[1:]))
     return ret[torch.randperm(ret.shape[0])] if shuffle else ret
 
+
+def define_tempering_utils(mean, var, target_log_prob, target_score=None):
+    """experiments/benchmark_utils.py:427-456: the Gaussian prior N(mean, var) -- ``Gauss`` for a vector of variances, ``GaussFull`` for a
+    covariance matrix -- and the geometric path (t, x) -> (t log p_prior + (1 - t) log pi~, its gradient): t is the weight of the PRIOR.
+    When ``target_log_prob`` is a bound ``unnorm_log_prob`` / ``log_prob`` of a distribution the engine knows (``engine.resolve_logp``), not a
+    checkerboard, and ``mean`` is on the GPU, the path is ``hip_tempered_log_prob_and_grads(target, prior)`` at weight 1 - t of the target, so
+    ``smc_sampler`` / ``re_sampler`` run whole levels as native moves.  Otherwise -- an opaque callable, or the checkerboard, which the
+    one-launch moves refuse -- it is the reference's closure (``target_score`` when given, autograd of ``target_log_prob`` otherwise,
+    ``sdeng_dist_eval`` for a checkerboard on the GPU), which the samplers compose move by move on the host."""
+    from .. import engine as E
+    from ..additions import ebm_mle
+    from ..distr.gauss import Gauss, GaussFull
+    dim = mean.shape[0]
+    if len(var.shape) == 2:
+        prior = GaussFull(dim=dim, loc=mean, cov=var).to(mean.device)
+    else:
+        prior = Gauss(dim=dim, loc=mean, scale=var.sqrt()).to(mean.device)
+    resolved = E.resolve_logp(target_log_prob)
+    known = None
+    if resolved is not None and resolved[1] is None:
+        try:
+            E.dist_desc(resolved[0], mean.device, [])
+            known = resolved[0]
+        except E.UnsupportedByEngine:
+            known = None
+    on_gpu = mean.is_cuda
+    if known is not None and on_gpu and type(known).__name__ != "Checkerboard":
+        hip = ebm_mle.hip_tempered_log_prob_and_grads(known, prior)
+
+        def log_prob_and_grads(t, x):
+            return hip(1.0 - t, x)
+        # (no hip_pair here: the samplers hand the kernel their times as weights of the TARGET; run_smc_sampler / run_re_sampler pass
+        # ``hip_path`` itself with 1 - times)
+        log_prob_and_grads.hip_path = hip
+        return prior, log_prob_and_grads
+
+    if known is not None and on_gpu:  # the checkerboard: log-density and (zero) score from the HIP kernel, moves composed on the host
+        def target_log_prob_and_grad(y):
+            lp, sc = E.dist_eval(known, y.detach())
+            return lp.flatten(), sc
+    elif target_score is None:
+        def target_log_prob_and_grad(y):
+            with torch.enable_grad():
+                y_ = y.detach().clone().requires_grad_(True)
+                log_prob_y = target_log_prob(y_).flatten()
+                return log_prob_y.detach(), torch.autograd.grad(log_prob_y.sum(), y_)[0].detach()
+    else:
+        def target_log_prob_and_grad(y):
+            return target_log_prob(y).flatten(), target_score(y)
+
+    def log_prob_and_grads(t, x):  # :441-454
+        log_prob_t, grad_t = target_log_prob_and_grad(x)
+        log_prob_p = prior.log_prob(x).flatten()
+        grad_p = prior.score(x)
+        log_prob = t.flatten() * log_prob_p + (1.0 - t).flatten() * log_prob_t
+        grad = t * grad_p + (1.0 - t) * grad_t
+        return log_prob, grad
+
+    return prior, log_prob_and_grads
+
+
+def _tempering_path(log_prob_and_grads, n_steps, n_chains, device):
+    """:463-464, :483-484: linspace(0, 1) weights of the prior, one per level and chain, with the path that reads them.  The engine path
+    (``hip_tempered_log_prob_and_grads``) takes the weight of the target, so it gets 1 - times: level 0 is the target either way."""
+    times = torch.linspace(0.0, 1.0, n_steps).view((-1, 1, 1)).to(device).repeat((1, n_chains, 1))
+    hip = getattr(log_prob_and_grads, "hip_path", None)
+    return (log_prob_and_grads, times) if hip is None else (hip, 1.0 - times)
+
+
+def run_smc_sampler(mean, var, n_steps, step_size, n_particles, n_mcmc_steps, n_warmup_mcmc_steps, target_log_prob, target_score=None,
+                    reweight_threshold=1.0, target_acceptance=0.75, verbose=False):
+    """experiments/benchmark_utils.py:459-476: annealed SMC from N(mean, var) (level n_steps - 1) to the target (level 0); returns the
+    target level's samples [n_mcmc_steps, n_particles, d]."""
+    from ..additions.ebm_mle import smc_sampler
+    prior, log_prob_and_grads = define_tempering_utils(mean, var, target_log_prob, target_score=target_score)
+    step_sizes_per_noise = step_size * torch.ones((n_steps, n_particles, 1), device=mean.device)
+    log_prob_and_grads, times = _tempering_path(log_prob_and_grads, n_steps, n_particles, mean.device)
+    return smc_sampler(x_init=prior.sample((n_particles,)), times=times, log_prob_and_grads=log_prob_and_grads,
+                       n_warmup_mcmc_steps=n_warmup_mcmc_steps, n_mcmc_steps=n_mcmc_steps, step_sizes_per_noise=step_sizes_per_noise,
+                       per_noise_init=False, reweight_threshold=reweight_threshold, target_acceptance=target_acceptance, verbose=verbose)[0][0]
+
+
+def run_re_sampler(mean, var, n_steps, step_size, batch_size, swap_frequency, n_mcmc_steps, n_warmup_mcmc_steps, target_log_prob,
+                   target_score=None, target_acceptance=0.75, verbose=False):
+    """experiments/benchmark_utils.py:479-496: replica exchange over the same path; returns the target level's samples
+    [n_mcmc_steps, batch_size, d]."""
+    from ..additions.ebm_mle import re_sampler
+    prior, log_prob_and_grads = define_tempering_utils(mean, var, target_log_prob, target_score=target_score)
+    step_sizes_per_noise = step_size * torch.ones((n_steps, batch_size, 1), device=mean.device)
+    log_prob_and_grads, times = _tempering_path(log_prob_and_grads, n_steps, batch_size, mean.device)
+    return re_sampler(x_init=prior.sample((batch_size,)), times=times, log_prob_and_grads=log_prob_and_grads, swap_frequency=swap_frequency,
+                      n_warmup_mcmc_steps=n_warmup_mcmc_steps, n_mcmc_steps=n_mcmc_steps, step_sizes_per_noise=step_sizes_per_noise,
+                      per_noise_init=False, target_acceptance=target_acceptance, verbose=verbose)[0][0]
