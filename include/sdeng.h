@@ -456,6 +456,59 @@ int sdeng_mmd_median(const float* X, const float* Y, int32_t n, int32_t m, int32
                      size_t workspace_bytes, void* stream);
 size_t sdeng_mmd_median_workspace_bytes(int32_t n, int32_t d);
 
+/* Energy-based (tilted-potential) references: log-density and score of GMMTitledPotential / GaussTiltedPotential (models/reparam.py:277-520
+ * and :485-606; what net.unnorm_log_prob, net.unnorm_log_prob_and_grad and net(t, x) compute: models/reparam.py:354-482) around
+ * FourierMLP(num_layers=6, channels=128, GELU) (models/mlp.py:57-143), in ONE launch over M = n_times * rows_per_time rows; row r is the
+ * state x[r] at time r / rows_per_time -- the layout of sdeng_ctrl_vjp, and of replica exchange's levels x chains
+ * (additions/ebm_mle.py:440-446).  Per row, with s = sde.s(t), sigma^2 = sde.sigma_sq(t) and (s', sigma'^2) the same at t' = max(t, t_limit):
+ *     xs = (x - s mean_gauss) / c_i,  c_i = s sqrt(var_gauss + sigma^2)                                   scaling_input   reparam.py:420-424
+ *     v  = FourierMLP(t, xs):  h0 = W_in xs + b_in + TimeEmbed(t);  h_l = W_l gelu(h_{l-1}) + b_l (l = 1..4);  v = W_out gelu(h4) + b_out
+ *     base_lp = -<v, xs>  (tilt 'dot', :428-430);   base_grad = -(v + J^T xs) / c_i,  J = dv/dxs: one backward pass with cotangent xs
+ *     prior: log-density and score of the mixture noised to t' (sde.marginal_gmm_params, eq/sdes.py:208-307; weights renormalised,
+ *            reparam.py:376-418): diagonal variances [k,d], or full covariances in eigen form, covariance_c = P_c diag(D_c) P_c^T, noised
+ *            precision P_c diag(1 / (s'^2 (D_c + sigma'^2))) P_c^T (eq/sdes.py:232-239); k = 1 is GaussTiltedPotential (:571-606)
+ *     log_prob = prior_lp + f base_lp;   grad = prior_grad + f base_grad;   f = s(t) with use_s_t_scaling, else 1                  :457-476
+ * tinfo [n_times][5] = (t, s, sigma^2, s', sigma'^2), computed by the caller with the SDE object in fp32 as the reference does: the
+ * kernel knows no SDE kinds.  log_prob [M] and grad [M,d] are each optional (not both NULL); without grad the backward pass is skipped.
+ * SDENG_E_INVALID: null pointers, d outside [1,128], k outside [1,16], M != n_times * rows_per_time, wrong abi_version.
+ * SDENG_E_UNSUPPORTED (reason in sdeng_last_error): a net other than 6 layers x 128 channels, a tilt other than 'dot', use_scaling_factor.
+ * Workspace: the packed weight images first (SDENG_FLAG_REUSE_PACK in flags: those of an earlier call with the same parameters are still
+ * there), then the per-wave pre-activations of the backward pass.  States or activations beyond 65 504 are not guarded (NaN). */
+#define SDENG_TILT_DOT 0
+#define SDENG_TILT_SQ_NORM 1
+#define SDENG_TILT_SUM 2
+typedef struct sdeng_tilted {
+  int32_t abi_version;      /* SDENG_ABI_VERSION                                                    */
+  uint32_t flags;           /* SDENG_FLAG_REUSE_PACK or 0                                           */
+  int32_t M, n_times, rows_per_time, d;
+  int32_t k;                /* mixture components, 1..16                                            */
+  int32_t full_cov;         /* 0: vars = variances [k,d];  1: vars = eigenvalues D [k,d], eigvecs = P [k,d,d] (row-major, columns = vectors) */
+  int32_t num_layers, channels;       /* of the FourierMLP: 6 and 128                               */
+  int32_t tilt_type;        /* SDENG_TILT_*                                                         */
+  int32_t use_scaling_factor, use_s_t_scaling;
+  int32_t reserved;
+  const float* x;           /* [M,d]                                                                */
+  const float* tinfo;       /* [n_times][5]                                                         */
+  const float *w_in, *b_in; /* input_embed [128,d], [128]                                           */
+  const float* w_h[4];      /* hidden_layer.0..3 [128,128]                                          */
+  const float* b_h[4];      /* [128]                                                                */
+  const float *w_out, *b_out;         /* out_layer [d,128], [d]                                     */
+  const float *te_coeff, *te_phase;   /* timestep_embed.timestep_coeff / _phase [128]               */
+  const float *te_w1, *te_b1;         /* timestep_embed.hidden_layer.0 [128,256], [128]             */
+  const float *te_w2, *te_b2;         /* timestep_embed.out_layer [128,128], [128]                  */
+  const float *mean_gauss, *var_gauss; /* [d] moments of the un-noised prior (scaling_input)         */
+  const float* weights;     /* [k] unnormalised                                                     */
+  const float* means;       /* [k,d]                                                                */
+  const float* vars;        /* [k,d]                                                                */
+  const float* eigvecs;     /* [k,d,d] with full_cov, else NULL                                     */
+  float* log_prob;          /* [M] or NULL                                                          */
+  float* grad;              /* [M,d] or NULL                                                        */
+  void* workspace;
+  size_t workspace_bytes;
+} sdeng_tilted;
+int sdeng_tilted_eval(const sdeng_tilted* desc, void* stream);
+size_t sdeng_tilted_eval_workspace_bytes(const sdeng_tilted* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ SPLIT_TILES_MAX_B = 8192  # SDENG_FLAG_SPLIT_TILES is honoured up to this batch 
 CTRL_CLIPPED, CTRL_SCORE, CTRL_LERP, CTRL_NONE, CTRL_CANCEL_DRIFT = 0, 1, 2, 3, 4
 REF_NONE, REF_GAUSS_DIAG, REF_GMM_DIAG, REF_GMM_FULL = 0, 1, 2, 3
 
+TILT_DOT, TILT_SQ_NORM, TILT_SUM = 0, 1, 2
+
 E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = -1, -2, -3, -4
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -72,6 +74,15 @@ class SinkhornResult(C.Structure):  # sdeng_sinkhorn_result (include/sdeng.h)
                 ("materialised", C.c_int32)]
 
 
+class Tilted(C.Structure):  # sdeng_tilted (include/sdeng.h)
+    _fields_ = [("abi_version", C.c_int32), ("flags", C.c_uint32)] + \
+        [(n, C.c_int32) for n in ("M", "n_times", "rows_per_time", "d", "k", "full_cov", "num_layers", "channels", "tilt_type",
+                                  "use_scaling_factor", "use_s_t_scaling", "reserved")] + \
+        [("x", _fp), ("tinfo", _fp), ("w_in", _fp), ("b_in", _fp), ("w_h", _fp * 4), ("b_h", _fp * 4)] + \
+        [(n, _fp) for n in ("w_out", "b_out", "te_coeff", "te_phase", "te_w1", "te_b1", "te_w2", "te_b2", "mean_gauss", "var_gauss",
+                            "weights", "means", "vars", "eigvecs", "log_prob", "grad", "workspace")] + [("workspace_bytes", C.c_size_t)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"sdeng error {code}: {msg}")
@@ -86,7 +97,8 @@ EXPORTS = ["sdeng_abi_version", "sdeng_last_error", "sdeng_workspace_bytes", "sd
            "sdeng_philox_normal", "sdeng_philox_normal_steps", "sdeng_sample_x0", "sdeng_ctrl_vjp", "sdeng_ctrl_vjp_workspace_bytes",
            "sdeng_langevin_moves", "sdeng_langevin_moves_workspace_bytes", "sdeng_kl_adjoint", "sdeng_kl_adjoint_workspace_bytes",
            "sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes",
-           "sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes", "sdeng_rwmh_moves", "sdeng_rwmh_moves_workspace_bytes"]
+           "sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes", "sdeng_rwmh_moves", "sdeng_rwmh_moves_workspace_bytes",
+           "sdeng_tilted_eval", "sdeng_tilted_eval_workspace_bytes"]
 
 
 def lib() -> C.CDLL:
@@ -152,6 +164,10 @@ def lib() -> C.CDLL:
     L.sdeng_mmd_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.sdeng_mmd_median_workspace_bytes.restype = C.c_size_t
     L.sdeng_mmd_median_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.sdeng_tilted_eval.restype = C.c_int
+    L.sdeng_tilted_eval.argtypes = [C.POINTER(Tilted), C.c_void_p]
+    L.sdeng_tilted_eval_workspace_bytes.restype = C.c_size_t
+    L.sdeng_tilted_eval_workspace_bytes.argtypes = [C.POINTER(Tilted)]
     if L.sdeng_abi_version() != ABI_VERSION:
         raise ImportError(f"libsdeng.so ABI {L.sdeng_abi_version()} != binding ABI {ABI_VERSION}")
     _LIB = L

@@ -1,7 +1,8 @@
 """Annealed samplers of ``sde_sampler/additions/ebm_mle.py``: ``smc_sampler`` (:11-195, annealed Langevin / sequential
 Monte Carlo), ``make_re_pairings`` (:198-216), ``re_step`` (:219-266) and ``re_sampler`` (:269-400, replica exchange), on top
 of the local moves of ``additions/mcmc.py``.  They are host compositions: what costs time is ``log_prob_and_grads(t, x)`` at
-every proposal, which ``hip_tempered_log_prob_and_grads`` serves from the HIP distribution kernels (no autograd).
+every proposal, which ``hip_tempered_log_prob_and_grads`` serves from the HIP distribution kernels and ``ebm_log_prob_and_grads``,
+for an energy-based reference, from ``sdeng_tilted_eval`` (no autograd either way).
 
 Same arguments, return values, random-number consumption order and diagnostics as the reference, including the
 preconditioned moves (``precond_matrix_per_noise``) and the PDDS transition and weights (``use_pdds_weights``).  Not provided:
@@ -275,3 +276,17 @@ def re_sampler(x_init, times, log_prob_and_grads, swap_frequency, n_warmup_mcmc_
     if not use_ula:
         diags["local_acc"] = mean_local_accs
     return samples, step, diags
+
+
+def ebm_log_prob_and_grads(net):
+    """The ``log_prob_and_grads(t, x)`` callable ``smc_sampler`` / ``re_sampler`` take, for an energy-based reference ``net``
+    (``GMMTitledPotential`` / ``GaussTiltedPotential``): mirror of ``MaximumLikelihoodEBM.log_prob_and_grads``
+    (additions/ebm_mle.py:440-446), served by one ``sdeng_tilted_eval`` launch per call -- no autograd.  The samplers' host loops call it
+    once per move."""
+    if not getattr(net, "has_unnorm_log_prob_and_grad", False):
+        raise E.UnsupportedByEngine("ebm_log_prob_and_grads: the net has no unnorm_log_prob_and_grad (autograd energies are not on the HIP path)")
+
+    def fn(t, x):
+        with torch.no_grad():
+            return E.tilted_eval(net, t, x.detach())
+    return fn

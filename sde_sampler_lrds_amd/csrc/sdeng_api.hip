@@ -19,6 +19,7 @@
 #include "grad_kernel.hpp"
 #include "cmcd_adjoint_kernel.hpp"
 #include "metric_kernels.hpp"
+#include "tilted_kernel.hpp"
 
 int sd_launch_logreg_images(const float* X, const float* y, int n, int dw, int NT, float* image, float* y_pad, hipStream_t s);
 int sd_launch_pack_square(const float* P, const float* loc, int d, int NT, float* out, float* loc_pad, hipStream_t s);
@@ -1162,5 +1163,98 @@ extern "C" int sdeng_mmd_median(const float* X, const float* Y, int32_t n, int32
   a.hist = reinterpret_cast<unsigned long long*>(ws + L.hist); a.state = reinterpret_cast<unsigned long long*>(ws + L.state);
   a.part = reinterpret_cast<double*>(ws + L.part); a.out = out;
   SD_HIP(sd_run_mmd_median(a, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+// ---- energy-based (tilted-potential) references: tilted_kernel.hpp ---------------------------------------------------------------
+struct TiltedLayout {
+  size_t pack, consts, trash, hbuf, total;  // floats
+  int ntiles, waves, grid, nimg;
+};
+static TiltedLayout tilted_layout(const sdeng_tilted* t) {
+  TiltedLayout L;
+  L.ntiles = (t->M + 15) / 16;
+  L.waves = sd_tilted_waves(L.ntiles);
+  L.grid = sd_tilted_grid(L.ntiles, L.waves);
+  L.nimg = TL_EIG + (t->full_cov ? 2 * t->k : 0);
+  size_t o = 0;
+  L.pack = o; o += static_cast<size_t>(L.nimg) * TL_SLOT;
+  L.consts = o; o += align64(TL_C_TOTAL);
+  L.trash = o; o += align64(512 * 4);
+  L.hbuf = o; o += t->grad ? static_cast<size_t>(L.grid) * L.waves * TL_HBUF_FLOATS : 0;
+  L.total = o;
+  return L;
+}
+static int check_tilted(const sdeng_tilted* t) {
+  if (!t) return fail(SDENG_E_INVALID, "tilted_eval: null descriptor");
+  if (t->abi_version != SDENG_ABI_VERSION) return fail(SDENG_E_INVALID, "ABI version %d, library has %d", t->abi_version, SDENG_ABI_VERSION);
+  if (t->d < 1 || t->d > 128) return fail(SDENG_E_INVALID, "tilted_eval: d = %d outside [1, 128]", t->d);
+  if (t->k < 1 || t->k > TL_KMAX) return fail(SDENG_E_INVALID, "tilted_eval: k = %d components outside [1, %d]", t->k, TL_KMAX);
+  if (t->M < 1 || t->n_times < 1 || t->rows_per_time < 1 || static_cast<long long>(t->n_times) * t->rows_per_time != t->M)
+    return fail(SDENG_E_INVALID, "tilted_eval: M = %d rows is not n_times * rows_per_time = %d * %d", t->M, t->n_times, t->rows_per_time);
+  if (static_cast<long long>(t->M) * t->d >= (1ll << 31)) return fail(SDENG_E_UNSUPPORTED, "tilted_eval: rows * d >= 2^31");
+  if (t->num_layers != 6 || t->channels != TL_H)
+    return fail(SDENG_E_UNSUPPORTED, "tilted_eval: the kernel is built for FourierMLP(num_layers=6, channels=128), got num_layers=%d channels=%d",
+                t->num_layers, t->channels);
+  if (t->tilt_type != SDENG_TILT_DOT) return fail(SDENG_E_UNSUPPORTED, "tilted_eval: tilt_type 'dot' only (type %d given)", t->tilt_type);
+  if (t->use_scaling_factor) return fail(SDENG_E_UNSUPPORTED, "tilted_eval: use_scaling_factor (the DRL scaling argument) is not supported");
+  const void* need[] = {t->x, t->tinfo, t->w_in, t->b_in, t->w_out, t->b_out, t->te_coeff, t->te_phase, t->te_w1, t->te_b1, t->te_w2, t->te_b2,
+                        t->mean_gauss, t->var_gauss, t->weights, t->means, t->vars, t->w_h[0], t->w_h[1], t->w_h[2], t->w_h[3],
+                        t->b_h[0], t->b_h[1], t->b_h[2], t->b_h[3]};
+  for (const void* p : need)
+    if (!p) return fail(SDENG_E_INVALID, "tilted_eval: null pointer in the descriptor");
+  if (t->full_cov && !t->eigvecs) return fail(SDENG_E_INVALID, "tilted_eval: full_cov without eigvecs");
+  if (!t->log_prob && !t->grad) return fail(SDENG_E_INVALID, "tilted_eval: nothing to compute (log_prob and grad are both NULL)");
+  return 0;
+}
+extern "C" size_t sdeng_tilted_eval_workspace_bytes(const sdeng_tilted* t) {
+  if (check_tilted(t)) return 0;
+  return tilted_layout(t).total * sizeof(float);
+}
+extern "C" int sdeng_tilted_eval(const sdeng_tilted* t, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SD_TRY(check_tilted(t));
+  const TiltedLayout L = tilted_layout(t);
+  const size_t need = L.total * sizeof(float);
+  if (!t->workspace || t->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", t->workspace_bytes, need);
+  float* ws = static_cast<float*>(t->workspace);
+  const int d = t->d, H = TL_H;
+  if (!(t->flags & SDENG_FLAG_REUSE_PACK)) {
+    TiltedPackArgs p;
+    memset(&p, 0, sizeof(p));
+    p.pack = ws + L.pack; p.consts = ws + L.consts;
+    p.coeff = t->te_coeff; p.phase = t->te_phase; p.mean_gauss = t->mean_gauss; p.var_gauss = t->var_gauss;
+    p.weights = t->weights; p.means = t->means; p.vars = t->vars; p.d = d; p.K = t->k;
+    int n = 0;
+    auto job = [&](int slot, const float* W, int n_out, int n_in, int ld, int col0, int transpose, int scale_n, const float* bias, int bias_off) {
+      TiltedPackJob& j = p.job[n++];
+      j.src = W; j.scale_src = W; j.bias = bias; j.n_out = n_out; j.n_in = n_in; j.ld = ld; j.col0 = col0; j.transpose = transpose;
+      j.scale_n = scale_n; j.slot = slot; j.bias_off = bias ? bias_off : -1;
+    };
+    job(TL_TE1S, t->te_w1, H, H, 2 * H, 0, 0, 2 * H * H, t->te_b1, TL_C_BTE1);  // the sine and cosine halves share the matrix's scale
+    job(TL_TE1C, t->te_w1, H, H, 2 * H, H, 0, 2 * H * H, nullptr, 0);
+    job(TL_TE2, t->te_w2, H, H, H, 0, 0, H * H, t->te_b2, TL_C_BTE2);
+    job(TL_WIN, t->w_in, H, d, d, 0, 0, H * d, t->b_in, TL_C_BIN);
+    for (int l = 0; l < 4; ++l) job(TL_WH + l, t->w_h[l], H, H, H, 0, 0, H * H, t->b_h[l], TL_C_BH + 128 * l);
+    job(TL_WOUT, t->w_out, d, H, H, 0, 0, d * H, t->b_out, TL_C_BOUT);
+    job(TL_WOUT_T, t->w_out, H, d, H, 0, 1, d * H, nullptr, 0);  // W_out^T: [128 x d]
+    for (int l = 0; l < 4; ++l) job(TL_WH_T + l, t->w_h[l], H, H, H, 0, 1, H * H, nullptr, 0);
+    job(TL_WIN_T, t->w_in, d, H, d, 0, 1, H * d, nullptr, 0);    // W_in^T: [d x 128]
+    if (t->full_cov)
+      for (int k = 0; k < t->k; ++k) {
+        const float* P = t->eigvecs + static_cast<size_t>(k) * d * d;
+        job(TL_EIG + 2 * k, P, d, d, d, 0, 1, d * d, nullptr, 0);      // y = P^T z
+        job(TL_EIG + 2 * k + 1, P, d, d, d, 0, 0, d * d, nullptr, 0);  // P q
+      }
+    p.njobs = n;
+    SD_HIP(sd_launch_tilted_pack(p, s));
+  }
+  TiltedArgs a;
+  memset(&a, 0, sizeof(a));
+  a.M = t->M; a.B = t->rows_per_time; a.d = d; a.N = t->n_times; a.K = t->k; a.full = t->full_cov ? 1 : 0;
+  a.use_st = t->use_s_t_scaling ? 1 : 0; a.ntiles = L.ntiles;
+  a.x = t->x; a.tinfo = t->tinfo; a.pack = ws + L.pack; a.consts = ws + L.consts;
+  a.hbuf = t->grad ? ws + L.hbuf : nullptr; a.log_prob = t->log_prob; a.grad = t->grad; a.trash = ws + L.trash;
+  SD_HIP(sd_launch_tilted(a, tiles_exact(d), L.grid, L.waves, s));
   return 0;
 }

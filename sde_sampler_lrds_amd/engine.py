@@ -1154,3 +1154,154 @@ def ctrl_forward(ctrl, t: float, x: torch.Tensor, score_gain=1.0, lerp_w=0.0):
     L.check(lib.sdeng_ctrl_forward(C.byref(desc), float(t), float(score_gain), float(lerp_w), xin.data_ptr(), out.data_ptr(),
                                    _stream_ptr(device)))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# energy-based (tilted-potential) references: GMMTitledPotential / GaussTiltedPotential (models/reparam.py:277-606)
+# ------------------------------------------------------------------------------------------------
+_TILTS = {"dot": L.TILT_DOT, "sq_norm": L.TILT_SQ_NORM}
+_TILTED_CLASSES = ("GMMTitledPotential", "GaussTiltedPotential")
+
+
+def _tilted_mixture(net):
+    """(weights [K], means [K,d], vars [K,d], eigvecs [K,d,d] or None) of the prior of a tilted potential, full covariances in the
+    eigen form (D, P): as given (``use_full_decomp``), or decomposed in float64 once per parameter version (``_EIGH``)."""
+    if _name(net) == "GaussTiltedPotential":
+        weights, means, var = torch.ones(1, device=net.mean.device), net.mean.reshape(1, -1), net.variance.unsqueeze(0)
+        full = bool(getattr(net, "is_full_cov_type", False))
+    else:
+        weights, means, var = net.weights, net.means, net.variances
+        full = bool(getattr(net, "is_full_gmm_type", False))
+    if not full:
+        return weights, means, var, None
+    if getattr(net, "use_full_decomp", False):
+        D, P = net.cov_D, net.cov_P
+        return weights, means, D.reshape(means.shape), P.reshape(means.shape[0], means.shape[1], means.shape[1])
+    src = net.variance if _name(net) == "GaussTiltedPotential" else net.variances
+    eig = _EIGH.get(src, lambda v: torch.linalg.eigh(v.detach().double()))
+    return weights, means, eig[0].float().reshape(means.shape), eig[1].float().reshape(means.shape[0], means.shape[1], means.shape[1])
+
+
+def tilted_desc(net, device, keep) -> L.Tilted:
+    """Tilted-potential object -> sdeng_tilted without its per-call fields (x, tinfo, outputs, workspace).  Accepts this package's
+    classes and the reference's own objects, by class name and attributes."""
+    if _name(net) not in _TILTED_CLASSES:
+        raise UnsupportedByEngine(f"tilted_eval: {_name(net)} is not a GMMTitledPotential / GaussTiltedPotential")
+    base = net.base_model
+    if _name(base) != "FourierMLP" or not hasattr(base, "timestep_embed"):
+        raise UnsupportedByEngine(f"tilted_eval: base_model must be a FourierMLP, got {_name(base)}")
+    if _name(base.activation) != "GELU" or getattr(base.activation, "approximate", "none") != "none":
+        raise UnsupportedByEngine("tilted_eval: the kernel evaluates the exact GELU only")
+    te = base.timestep_embed
+    d = L.Tilted()
+    d.abi_version = L.ABI_VERSION
+    d.d = int(net.dim)
+    d.num_layers, d.channels = len(base.hidden_layer) + 2, int(base.channels)
+    d.tilt_type = _TILTS.get(net.tilt_type, L.TILT_SUM)
+    d.use_scaling_factor, d.use_s_t_scaling = int(bool(net.use_scaling_factor)), int(bool(net.use_s_t_scaling))
+    if len(te.hidden_layer) != 1 or int(te.channels) != int(base.channels):
+        raise UnsupportedByEngine("tilted_eval: the time embedding must be TimeEmbed(num_layers=2) of the net's width")
+    weights, means, var, eigvecs = _tilted_mixture(net)
+    d.k, d.full_cov = int(means.shape[0]), int(eigvecs is not None)
+    d.w_in, d.b_in = _dev_f32(base.input_embed.weight, device, keep), _dev_f32(base.input_embed.bias, device, keep)
+    for i, layer in enumerate(list(base.hidden_layer)[:4]):
+        d.w_h[i], d.b_h[i] = _dev_f32(layer.weight, device, keep), _dev_f32(layer.bias, device, keep)
+    d.w_out, d.b_out = _dev_f32(base.out_layer.weight, device, keep), _dev_f32(base.out_layer.bias, device, keep)
+    d.te_coeff, d.te_phase = _dev_f32(te.timestep_coeff.reshape(-1), device, keep), _dev_f32(te.timestep_phase.reshape(-1), device, keep)
+    d.te_w1, d.te_b1 = _dev_f32(te.hidden_layer[0].weight, device, keep), _dev_f32(te.hidden_layer[0].bias, device, keep)
+    d.te_w2, d.te_b2 = _dev_f32(te.out_layer.weight, device, keep), _dev_f32(te.out_layer.bias, device, keep)
+    d.mean_gauss, d.var_gauss = _dev_f32(net.mean_gauss.reshape(-1), device, keep), _dev_f32(net.var_gauss.reshape(-1), device, keep)
+    d.weights, d.means, d.vars = _dev_f32(weights, device, keep), _dev_f32(means, device, keep), _dev_f32(var, device, keep)
+    d.eigvecs = _dev_f32(eigvecs, device, keep) if eigvecs is not None else None
+    return d
+
+
+def tilted_times(net, t: torch.Tensor, M: int, per_row=False):
+    """``t`` (scalar, (1,1) or M values) -> (n_times, rows_per_time, tinfo [n_times,5] float32 on the CPU).  Runs of equal consecutive
+    times of equal length become (N, B); anything else -- or everything, with ``per_row`` -- N = M, B = 1.  The five scalars per time -- t, s(t), sigma_sq(t) and the last two
+    at max(t, t_limit) -- are the SDE object's own float32 expressions (models/reparam.py:361, :422-423)."""
+    tf = t.detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    if tf.numel() == 1 and not per_row:
+        tu, B = tf, M
+    elif per_row and tf.numel() in (1, M):
+        tu, B = tf.expand(M), 1
+    elif tf.numel() == M:
+        change = torch.nonzero(tf[1:] != tf[:-1]).reshape(-1) + 1
+        starts = torch.cat([torch.zeros(1, dtype=torch.long), change])
+        lengths = torch.diff(torch.cat([starts, torch.tensor([M])]))
+        if bool((lengths == lengths[0]).all()):
+            tu, B = tf[starts], int(lengths[0])
+        else:
+            tu, B = tf, 1
+    else:
+        raise ValueError(f"tilted_eval: t has {tf.numel()} values for {M} rows (a scalar, (1, 1) or one per row)")
+    sde = _cpu_sde(net.sde)
+    tc = tu.reshape(-1, 1)
+    tl = torch.maximum(tc, float(net.t_limit) * torch.ones_like(tc))
+    cols = [tc, sde.s(tc), sde.sigma_sq(tc), sde.s(tl), sde.sigma_sq(tl)]
+    tinfo = torch.cat([c.to(torch.float32).expand(tc.shape[0], 1) if torch.is_tensor(c) else torch.full_like(tc, float(c)) for c in cols], dim=1)
+    return int(tu.numel()), B, tinfo.contiguous()
+
+
+_TILTED_TIMES = _TensorCache()
+_TILTED_PACKS = weakref.WeakKeyDictionary()  # net -> (parameter versions, workspace holding its packed images)
+
+
+def _tilted_versions(net, device):
+    return tuple((id(p), p._version, p.data_ptr(), str(p.device)) for p in list(net.parameters()) + list(net.buffers())) + (str(device),)
+
+
+def tilted_needs_param_grad(net) -> bool:
+    return torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters())
+
+
+def tilted_eval(net, t, x: torch.Tensor, want_grad=True, want_logp=True, per_row_times=False):
+    """sdeng_tilted_eval: (log_prob [M], grad [M,d]) of an energy-based reference at the rows (t, x), in one HIP launch -- what
+    ``net.unnorm_log_prob_and_grad(t, x)`` computes with autograd in the reference (models/reparam.py:457-476).  The packed weight
+    images live in a workspace of the net's own and are re-made only when a parameter or buffer changed.  ``per_row_times``: present the
+    rows as N = M times of one row each whatever ``t`` holds (same results; for tests)."""
+    if tilted_needs_param_grad(net):
+        raise UnsupportedByEngine("tilted_eval computes no gradient with respect to the net's parameters: call it under torch.no_grad() "
+                                  "or with requires_grad_(False) parameters (training an EBM is not on the HIP path)")
+    require_gpu(x)
+    lib = L.lib()
+    device, keep = x.device, []
+    xin = _f32c(x)
+    if xin.dim() != 2:
+        raise ValueError("tilted_eval: x must be [M, d]")
+    M, dim = xin.shape
+    t = torch.as_tensor(t)
+    # the time table of a tensor the samplers pass again and again is made once (reading a device tensor back waits for the stream)
+    def table(tt, per_row=False):
+        n, b, info = tilted_times(net, tt, M, per_row)
+        return n, b, info.to(device)
+    owner, rows, times = _TILTED_TIMES.get(t, lambda tt: (weakref.ref(net), (M, str(device)), table(tt)))
+    n_times, B, tdev = times if owner() is net and rows == (M, str(device)) and not per_row_times else table(t, per_row_times)
+    d = tilted_desc(net, device, keep)
+    if d.d != dim:
+        raise ValueError(f"tilted_eval: x has {dim} features, the potential {d.d}")
+    d.M, d.n_times, d.rows_per_time = M, n_times, B
+    keep.append(tdev)
+    d.x, d.tinfo = xin.data_ptr(), tdev.data_ptr()
+    logp = torch.empty(M, dtype=torch.float32, device=device) if want_logp else None
+    grad = torch.empty(M, dim, dtype=torch.float32, device=device) if want_grad else None
+    d.log_prob, d.grad = (logp.data_ptr() if want_logp else None), (grad.data_ptr() if want_grad else None)
+    need = lib.sdeng_tilted_eval_workspace_bytes(C.byref(d))
+    if need == 0:
+        rc = lib.sdeng_tilted_eval(C.byref(d), _stream_ptr(device))  # the descriptor is rejected: fetch the code and the reason
+        if rc == L.E_UNSUPPORTED:
+            raise UnsupportedByEngine(lib.sdeng_last_error().decode())
+        L.check(rc)
+    versions = _tilted_versions(net, device)
+    hit = _TILTED_PACKS.get(net)
+    if hit is not None and hit[0] == versions and hit[1].numel() >= need:
+        ws, d.flags = hit[1], L.FLAG_REUSE_PACK
+    else:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        _TILTED_PACKS[net] = (versions, ws)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    rc = lib.sdeng_tilted_eval(C.byref(d), _stream_ptr(device))
+    if rc == L.E_UNSUPPORTED:
+        raise UnsupportedByEngine(lib.sdeng_last_error().decode())
+    L.check(rc)
+    return logp, grad
