@@ -509,6 +509,26 @@ typedef struct sdeng_tilted {
 int sdeng_tilted_eval(const sdeng_tilted* desc, void* stream);
 size_t sdeng_tilted_eval_workspace_bytes(const sdeng_tilted* desc);
 
+/* Training an energy-based reference: everything the gradient of the energy with respect to the net's parameters needs, in ONE launch --
+ * the training instantiation of the kernel behind sdeng_tilted_eval, same walk, same numbers.  The trainer's loss (MaximumLikelihoodEBM.train,
+ * additions/ebm_mle.py:735-771) is a function of E_r = net.energy(t_r, x_r) over detached rows; the prior has no parameters, so with the
+ * quantities of sdeng_tilted_eval (models/reparam.py:426-451)
+ *     E_r = -prior_lp_r + f_r <v_r, xs_r>,   dE_r/dtheta = f_r (backward pass of the net with cotangent xs_r)
+ * -- the backward pass J^T xs of sdeng_tilted_eval, whose pre-activation cotangents dh_4 .. dh_0 are written out here instead of dropped.
+ * Per row (row-major arrays, row r as in sdeng_tilted):
+ *     a[l]  [M,128]  gelu(h_l), l = 0..4            d[l]  [M,128]  f_r dh_l,  dh_4 = (W_out^T xs) . gelu'(h_4),  dh_l = (W_{l+1}^T dh_{l+1}) . gelu'(h_l)
+ *     xs    [M,d]    the scaled state               dv    [M,d]    f_r xs, the cotangent of v
+ * With c_r = dL/dE_r (the caller's: the kernel knows no loss) the gradients are outer products over the rows, left to the caller as for
+ * sdeng_ctrl_vjp:  dW_out = (c dv)^T a[4],  dW_l = (c d[l])^T a[l-1] (l = 1..4),  dW_in = (c d[0])^T xs,  biases the column sums, and the
+ * time embedding takes sum_b c d[0] per time as the cotangent of TimeEmbed(t).
+ * desc->log_prob and desc->grad are written as by sdeng_tilted_eval and are each optional here (both may be NULL).  Errors: those of
+ * sdeng_tilted_eval, and SDENG_E_INVALID for a null `rows` or a null pointer in it (sdeng_last_error names the array).  Workspace: that of
+ * an evaluation with grad (the pre-activations are always kept); SDENG_FLAG_REUSE_PACK as for sdeng_tilted_eval -- the packed images of
+ * the two entry points are the same. */
+typedef struct sdeng_tilted_rows { float *a[5], *d[5]; float *xs, *dv; } sdeng_tilted_rows;
+int sdeng_tilted_vjp(const sdeng_tilted* desc, const sdeng_tilted_rows* rows, void* stream);
+size_t sdeng_tilted_vjp_workspace_bytes(const sdeng_tilted* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,10 @@ class Tilted(C.Structure):  # sdeng_tilted (include/sdeng.h)
                             "weights", "means", "vars", "eigvecs", "log_prob", "grad", "workspace")] + [("workspace_bytes", C.c_size_t)]
 
 
+class TiltedRows(C.Structure):  # sdeng_tilted_rows (include/sdeng.h)
+    _fields_ = [("a", _fp * 5), ("d", _fp * 5), ("xs", _fp), ("dv", _fp)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"sdeng error {code}: {msg}")
@@ -98,7 +102,7 @@ EXPORTS = ["sdeng_abi_version", "sdeng_last_error", "sdeng_workspace_bytes", "sd
            "sdeng_langevin_moves", "sdeng_langevin_moves_workspace_bytes", "sdeng_kl_adjoint", "sdeng_kl_adjoint_workspace_bytes",
            "sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes",
            "sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes", "sdeng_rwmh_moves", "sdeng_rwmh_moves_workspace_bytes",
-           "sdeng_tilted_eval", "sdeng_tilted_eval_workspace_bytes"]
+           "sdeng_tilted_eval", "sdeng_tilted_eval_workspace_bytes", "sdeng_tilted_vjp", "sdeng_tilted_vjp_workspace_bytes"]
 
 
 def lib() -> C.CDLL:
@@ -168,6 +172,10 @@ def lib() -> C.CDLL:
     L.sdeng_tilted_eval.argtypes = [C.POINTER(Tilted), C.c_void_p]
     L.sdeng_tilted_eval_workspace_bytes.restype = C.c_size_t
     L.sdeng_tilted_eval_workspace_bytes.argtypes = [C.POINTER(Tilted)]
+    L.sdeng_tilted_vjp.restype = C.c_int
+    L.sdeng_tilted_vjp.argtypes = [C.POINTER(Tilted), C.POINTER(TiltedRows), C.c_void_p]
+    L.sdeng_tilted_vjp_workspace_bytes.restype = C.c_size_t
+    L.sdeng_tilted_vjp_workspace_bytes.argtypes = [C.POINTER(Tilted)]
     if L.sdeng_abi_version() != ABI_VERSION:
         raise ImportError(f"libsdeng.so ABI {L.sdeng_abi_version()} != binding ABI {ABI_VERSION}")
     _LIB = L

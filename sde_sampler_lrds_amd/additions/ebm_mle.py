@@ -2,11 +2,12 @@
 Monte Carlo), ``make_re_pairings`` (:198-216), ``re_step`` (:219-266) and ``re_sampler`` (:269-400, replica exchange), on top
 of the local moves of ``additions/mcmc.py``.  They are host compositions: what costs time is ``log_prob_and_grads(t, x)`` at
 every proposal, which ``hip_tempered_log_prob_and_grads`` serves from the HIP distribution kernels and ``ebm_log_prob_and_grads``,
-for an energy-based reference, from ``sdeng_tilted_eval`` (no autograd either way).
+for an energy-based reference, from ``sdeng_tilted_eval`` (no autograd either way).  ``MaximumLikelihoodEBM`` (:401-808) is the
+trainer around them: its energies and their parameter gradients come from ``sdeng_tilted_vjp``, one launch per ``net.energy`` call.
 
 Same arguments, return values, random-number consumption order and diagnostics as the reference, including the
 preconditioned moves (``precond_matrix_per_noise``) and the PDDS transition and weights (``use_pdds_weights``).  Not provided:
-the ``MaximumLikelihoodEBM`` trainer around the samplers (an energy-net training loop, outside the simulate path)."""
+the trainer's ``'smc_pdds'`` sampler type (the reference's branch reads an undefined ``x_init``)."""
 from __future__ import annotations
 
 import torch
@@ -290,3 +291,249 @@ def ebm_log_prob_and_grads(net):
         with torch.no_grad():
             return E.tilted_eval(net, t, x.detach())
     return fn
+
+
+class MaximumLikelihoodEBM(torch.nn.Module):
+    """Maximum-likelihood training of an energy-based reference (mirror of additions/ebm_mle.py:401-808): positives are the data noised
+    to every level, negatives come from the annealed samplers above (``'annealed_mcmc'``, ``'smc'``, ``'replica_exchange'``) or from
+    Langevin chains started at the positives (``'cd'``), and the loss is mean(E(pos) - E(neg)) (+ ``reg_val`` mean(E^2)).  Same
+    constructor, attributes, arguments, return tuples and random-number consumption order as the reference (DataLoader shuffle,
+    ``randn_like`` for the positives, ``sample_prior`` on the very first batch, then the samplers).
+
+    On the engine every ``net.energy`` of ``train`` is one ``sdeng_tilted_vjp`` launch and its backward the products of
+    ``engine.tilted_param_grads`` (``net.param_grads`` is switched on for the duration of ``train``); the samplers evaluate through
+    ``net.unnorm_log_prob_and_grad`` (``sdeng_tilted_eval``) with the parameters frozen.  ``'smc_pdds'`` raises: the reference's branch
+    reads an ``x_init`` it never defines."""
+
+    def __init__(self, sde, prior, net, sampler_type, step_sizes_per_noise=1e-3, precond_matrix_per_noise=None,
+                 precond_matrix_chol_per_noise=None, use_ula=False, reweight_threshold=1.0, swap_frequency=16, target_acceptance=0.75,
+                 perc_keep_mcmc=-1.0, use_snr_adapted_disc=False, start_eps=1e-3, end_eps=0.0, n_steps=100):
+        super().__init__()
+        self.sde, self.prior = sde, prior
+        self.prior.cpu()
+        self.net = net.cpu()
+        self.sampler_type, self.reweight_threshold, self.swap_frequency = sampler_type, reweight_threshold, swap_frequency
+        self.step_sizes_per_noise = step_sizes_per_noise
+        self.precond_matrix_per_noise, self.precond_matrix_chol_per_noise = precond_matrix_per_noise, precond_matrix_chol_per_noise
+        self.use_precond = precond_matrix_per_noise is not None and precond_matrix_chol_per_noise is not None
+        self.use_ula, self.target_acceptance = use_ula, target_acceptance
+        self.use_snr_adapted_disc, self.perc_keep_mcmc = use_snr_adapted_disc, perc_keep_mcmc
+        self.start_eps, self.end_eps, self.n_steps = start_eps, end_eps, n_steps
+        self.build_time_disc()
+
+    def build_time_disc(self):
+        from ..utils.common import get_timesteps
+        kw = dict(sde=self.sde) if self.use_snr_adapted_disc else {}
+        self.register_buffer("times", get_timesteps(start=self.start_eps, end=self.sde.terminal_t - self.end_eps, steps=self.n_steps,
+                                                    **kw).unsqueeze(-1))
+
+    def log_prob_and_grads(self, t, y):
+        if self.net.has_unnorm_log_prob_and_grad:
+            return self.net.unnorm_log_prob_and_grad(t, y)
+        y_ = y.clone().requires_grad_(True)
+        lp = self.net.unnorm_log_prob(t, y_)
+        return lp, torch.autograd.grad(lp.sum(), y_)[0].detach()
+
+    def sample_model(self, batch_size, times_expanded, is_very_first_negative_sampling, initial_n_warmup_mcmc_steps, n_warmup_mcmc_steps,
+                     n_mcmc_steps, x_init_persistant):
+        if self.sampler_type == "smc_pdds":
+            raise NotImplementedError("sampler_type 'smc_pdds': the reference's branch reads an undefined x_init (additions/ebm_mle.py:487-503)")
+        if self.sampler_type not in ("annealed_mcmc", "smc", "replica_exchange"):
+            raise NotImplementedError("Sampler {} not found.".format(self.sampler_type))
+        frozen = [p.requires_grad for p in self.net.parameters()]
+        for p in self.net.parameters():
+            p.requires_grad_(False)
+        try:
+            common = dict(times=times_expanded, log_prob_and_grads=self.log_prob_and_grads,
+                          n_warmup_mcmc_steps=initial_n_warmup_mcmc_steps if is_very_first_negative_sampling else n_warmup_mcmc_steps,
+                          n_mcmc_steps=n_mcmc_steps, step_sizes_per_noise=self.step_sizes_per_noise, target_acceptance=self.target_acceptance,
+                          precond_matrix_per_noise=self.precond_matrix_per_noise if self.use_precond else None,
+                          precond_matrix_chol_per_noise=self.precond_matrix_chol_per_noise if self.use_precond else None,
+                          use_ula=self.use_ula, verbose=False)
+            if self.sampler_type == "replica_exchange":
+                xs_neg, self.step_sizes_per_noise, diags = re_sampler(x_init=x_init_persistant, swap_frequency=self.swap_frequency,
+                                                                      per_noise_init=True, **common)
+            else:
+                x_init = self.prior.sample((batch_size,))
+                xs_neg, self.step_sizes_per_noise, diags = smc_sampler(
+                    x_init=x_init, reweight_threshold=self.reweight_threshold if self.sampler_type == "smc" else 0.0, **common)
+        finally:
+            for p, state in zip(self.net.parameters(), frozen):
+                p.requires_grad_(state)
+        return xs_neg, diags
+
+    def cd_sampling(self, times_expanded, n_warmup_mcmc_steps, n_mcmc_steps, xs_pos):
+        ones = (1,) * (xs_pos.dim() - 1)
+        t_rows = times_expanded.reshape((-1, *ones))
+        def f(z):  # the chains carry no graph (train detaches them): evaluated like the samplers' moves, by sdeng_tilted_eval
+            with torch.no_grad():
+                return self.log_prob_and_grads(t_rows, z)
+        xs_neg = torch.empty((n_mcmc_steps, *xs_pos.shape), device=xs_pos.device)
+        x = xs_pos.clone()
+        lp, grad = f(x)
+        precond = (self.precond_matrix_per_noise, self.precond_matrix_chol_per_noise) if self.use_precond else None
+        move = _LocalMove(f, self.use_ula, self.target_acceptance, precond)
+        pgrad, acc = move.pgrad(grad), None
+        for it in range(n_warmup_mcmc_steps + n_mcmc_steps):
+            x, lp, grad, pgrad, self.step_sizes_per_noise, log_acc = move(x, lp, grad, pgrad, self.step_sizes_per_noise)
+            if log_acc is not None:
+                acc = torch.exp(torch.minimum(torch.zeros_like(log_acc), log_acc)).mean().cpu()
+            if it >= n_warmup_mcmc_steps:
+                xs_neg[it - n_warmup_mcmc_steps] = x.clone()
+        return xs_neg, ({} if self.use_ula else {"local_acc": acc})
+
+    def save_logs(self, losses, losses_grad, diagnostics, use_ema, epoch_id, ckpt_filepath_maker):
+        import pickle
+        torch.save({k: v.cpu() for k, v in self.net.state_dict().items()}, ckpt_filepath_maker(epoch_id))
+        if use_ema:
+            torch.save({k: v.cpu() for k, v in self.ema_net.state_dict().items()}, ckpt_filepath_maker(epoch_id, suffix="ema"))
+        torch.save(torch.FloatTensor(losses), ckpt_filepath_maker(epoch_id, suffix="losses"))
+        if losses_grad is not None:
+            torch.save(torch.FloatTensor(losses_grad), ckpt_filepath_maker(epoch_id, suffix="losses_grad"))
+        with open(ckpt_filepath_maker(epoch_id, suffix="diag"), "wb") as f:
+            pickle.dump(diagnostics, f)
+
+    def train(self, data, batch_size, n_epochs, reweight_loss=False, lr=3e-4, decay=0.0, clip_val=1.0, initial_n_warmup_mcmc_steps=1024,
+              n_mcmc_steps=32, n_accumulation_steps=1, reg_val=0.0, use_ema=False, ema_decay=0.995, ema_steps=10, ckpt_interval=-1,
+              ckpt_filepath_maker=None, verbose=True):
+        """additions/ebm_mle.py:590-801.  Returns (losses, gradient norms, diagnostics), or (losses, diagnostics) with ``clip_val <= 0``."""
+        cd = self.sampler_type == "cd"
+        if cd and n_accumulation_steps != 1:
+            raise ValueError("Can't use n_accumulation_steps != 1 if sampler_type is CD.")
+        if cd and reweight_loss:
+            raise NotImplementedError("Loss scaling not implemented with CD.")
+        if self.sampler_type == "smc_pdds":
+            raise NotImplementedError("sampler_type 'smc_pdds': the reference's branch reads an undefined x_init (additions/ebm_mle.py:487-503)")
+        if self.sampler_type not in ("annealed_mcmc", "smc", "replica_exchange", "cd"):
+            raise NotImplementedError("Sampler {} not found.".format(self.sampler_type))
+        E.require_gpu(data)
+        had = getattr(self.net, "param_grads", False)
+        self.net.param_grads = True
+        try:
+            return self._train(data, batch_size, n_epochs, reweight_loss, lr, decay, clip_val, initial_n_warmup_mcmc_steps, n_mcmc_steps,
+                               n_accumulation_steps, reg_val, use_ema, ema_decay, ema_steps, ckpt_interval, ckpt_filepath_maker, verbose)
+        finally:
+            self.net.param_grads = had
+
+    def _train(self, data, batch_size, n_epochs, reweight_loss, lr, decay, clip_val, initial_n_warmup_mcmc_steps, n_mcmc_steps,
+               n_accumulation_steps, reg_val, use_ema, ema_decay, ema_steps, ckpt_interval, ckpt_filepath_maker, verbose):
+        cd, n_levels, dev = self.sampler_type == "cd", self.times.shape[0], self.times.device
+        optimizer = (torch.optim.AdamW(self.net.parameters(), lr=lr, weight_decay=decay) if decay > 0
+                     else torch.optim.Adam(self.net.parameters(), lr=lr))
+        if self.perc_keep_mcmc > 0:
+            n_warmup, n_kept = int((1.0 - self.perc_keep_mcmc) * n_mcmc_steps), int(self.perc_keep_mcmc * n_mcmc_steps)
+        else:
+            n_warmup, n_kept = n_mcmc_steps - 1, 1
+        eff_bs = batch_size if cd else min(batch_size * n_kept, data.shape[0])
+        loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(data), batch_size=eff_bs, shuffle=True, drop_last=True)
+        n_batches = len(loader)
+        if use_ema:
+            alpha = min(1.0, (1.0 - ema_decay) * (n_accumulation_steps * n_levels * eff_bs * ema_steps / n_epochs))
+            self.ema_net = torch.optim.swa_utils.AveragedModel(self.net, multi_avg_fn=torch.optim.swa_utils.get_ema_multi_avg_fn(1.0 - alpha))
+            self.ema_net.module.param_grads = False  # the copy is for evaluation: the switch is train's, on the net it trains
+        data_shape, ones = data.shape[1:], (1,) * (data.dim() - 1)
+        per_level = lambda b: self.times.reshape((-1, 1, *ones)).repeat((1, b, *ones))  # noqa: E731
+        ts = per_level(eff_bs)
+        if cd:
+            ts_neg = per_level(min(batch_size * n_kept, data.shape[0])).view((-1, *ones))
+        times_expanded = per_level(batch_size)
+        mean_factor = self.sde.s(ts)
+        std_factor = mean_factor * torch.sqrt(self.sde.sigma_sq(ts))
+        ts = ts.view((-1, *ones))
+        # initial step sizes: one per level and chain
+        st = self.step_sizes_per_noise
+        if isinstance(st, float) or (torch.is_tensor(st) and st.dim() == 0):
+            self.step_sizes_per_noise = st * torch.ones((n_levels, batch_size, *ones), device=dev)
+        elif st.dim() > 0:
+            self.step_sizes_per_noise = st.flatten().unsqueeze(1).repeat((1, batch_size)).to(dev).view((n_levels, batch_size, *ones))
+        else:
+            raise ValueError("Wrong shape of step_sizes_per_noise.")
+        if cd:
+            self.step_sizes_per_noise = self.step_sizes_per_noise.view((-1, *ones))
+        if self.use_precond and self.sampler_type in ("replica_exchange", "cd"):  # one matrix per level -> one per chain
+            def per_chain(m):
+                m = m.unsqueeze(1).repeat((1, batch_size, *ones, *ones))
+                return m.view((-1, *data_shape, *data_shape)) if cd else m
+            self.precond_matrix_per_noise = per_chain(self.precond_matrix_per_noise)
+            self.precond_matrix_chol_per_noise = per_chain(self.precond_matrix_chol_per_noise)
+        x_persist = None
+        if self.sampler_type == "replica_exchange":  # persistent state of the replicas
+            if self.net.has_sample_prior:
+                t_rows = self.times.clone().reshape((-1, 1)).repeat((1, batch_size)).view((-1, 1))
+                x_persist = self.net.sample_prior(t_rows).view((n_levels, batch_size, -1))
+            else:
+                x_persist = self.prior.sample((n_levels, batch_size,))
+        if verbose:
+            from tqdm import trange
+            epochs = trange(n_epochs)
+        else:
+            epochs = range(n_epochs)
+        losses, losses_grad, diagnostics = [], ([] if clip_val > 0 else None), []
+        first_sampling, global_step = True, 0
+        tail = n_batches % n_accumulation_steps  # batches of the last, shorter accumulation group
+        for epoch_id in epochs:
+            for batch_id, batch in enumerate(loader):
+                samples = batch[0]
+                xs_pos = (mean_factor * samples.unsqueeze(0) + std_factor * torch.randn_like(samples)).view((-1, *data_shape))
+                fresh = batch_id % n_accumulation_steps == 0  # negatives (and their energies) are renewed once per accumulation group
+                if epoch_id == 0 and batch_id == 0 and self.net.has_sample_prior:
+                    xs_neg, diags = self.net.sample_prior(ts_neg if cd else ts), {}
+                elif fresh:
+                    warm = initial_n_warmup_mcmc_steps if first_sampling else n_warmup
+                    if cd:
+                        xs_neg, diags = self.cd_sampling(times_expanded=times_expanded, n_warmup_mcmc_steps=warm, n_mcmc_steps=n_kept,
+                                                         xs_pos=xs_pos)
+                        xs_neg = xs_neg.detach()
+                    else:
+                        xs_neg, diags = self.sample_model(batch_size=batch_size, times_expanded=times_expanded,
+                                                          is_very_first_negative_sampling=first_sampling,
+                                                          initial_n_warmup_mcmc_steps=initial_n_warmup_mcmc_steps, n_warmup_mcmc_steps=n_warmup,
+                                                          n_mcmc_steps=n_kept, x_init_persistant=x_persist)
+                        xs_neg = xs_neg.detach()
+                        if x_persist is not None:
+                            x_persist = xs_neg[:, -1]
+                    first_sampling = False
+                    diagnostics.append(diags)
+                    xs_neg = xs_neg.reshape((-1, *data_shape))
+                en_pos = self.net.energy(ts, xs_pos).flatten()
+                if fresh:
+                    en_neg = self.net.energy(ts_neg if cd else ts, xs_neg).flatten()
+                if cd:
+                    loss = en_pos.mean() - en_neg.mean()
+                else:
+                    scale = 1.0 / self.sde.sigma_sq(ts).flatten() if reweight_loss else 1.0
+                    loss = (scale * (en_pos - en_neg)).mean()
+                if reg_val > 0:
+                    loss = loss + reg_val * (torch.square(en_pos).mean() + torch.square(en_neg).mean())
+                loss = loss / (tail if batch_id >= n_batches - tail else n_accumulation_steps)  # the group's average
+                bad = "NaN loss detected." if torch.isnan(loss).any() else (
+                    "Training diverged (loss = {:.2e}).".format(loss.item()) if loss.abs().item() > 1e9 else None)
+                if bad:
+                    self.save_logs(losses, losses_grad, diagnostics, use_ema, epoch_id, ckpt_filepath_maker)
+                    raise RuntimeError(bad)
+                losses.append(loss.item())
+                loss.backward(retain_graph=n_accumulation_steps > 1)
+                infos = {"loss": losses[-1]}
+                if clip_val > 0:
+                    losses_grad.append(torch.nn.utils.clip_grad_norm_(self.net.parameters(), clip_val).item())
+                    infos["norm_grad_loss"] = losses_grad[-1]
+                if verbose:
+                    epochs.set_postfix(**infos, **{k: float(v.cpu().mean().item()) for k, v in diags.items()})
+                if (batch_id + 1) % n_accumulation_steps == 0 or batch_id + 1 == n_batches:
+                    optimizer.step()
+                    global_step += 1
+                    if use_ema and global_step % ema_steps == 0:
+                        self.ema_net.update_parameters(self.net)
+                    optimizer.zero_grad()
+            if ckpt_interval > 0 and epoch_id % ckpt_interval == 0:
+                self.save_logs(losses, losses_grad, diagnostics, use_ema, epoch_id, ckpt_filepath_maker)
+        if clip_val > 0:
+            return torch.FloatTensor(losses), torch.FloatTensor(losses_grad), diagnostics
+        return torch.FloatTensor(losses), diagnostics
+
+    def _apply(self, fn):
+        new_self = super()._apply(fn)
+        new_self.sde = new_self.sde._apply(fn)
+        new_self.prior._apply(fn)
+        new_self.net = new_self.net._apply(fn)
+        return new_self

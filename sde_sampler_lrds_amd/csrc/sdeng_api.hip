@@ -1171,7 +1171,7 @@ struct TiltedLayout {
   size_t pack, consts, trash, hbuf, total;  // floats
   int ntiles, waves, grid, nimg;
 };
-static TiltedLayout tilted_layout(const sdeng_tilted* t) {
+static TiltedLayout tilted_layout(const sdeng_tilted* t, bool train = false) {
   TiltedLayout L;
   L.ntiles = (t->M + 15) / 16;
   L.waves = sd_tilted_waves(L.ntiles);
@@ -1181,40 +1181,41 @@ static TiltedLayout tilted_layout(const sdeng_tilted* t) {
   L.pack = o; o += static_cast<size_t>(L.nimg) * TL_SLOT;
   L.consts = o; o += align64(TL_C_TOTAL);
   L.trash = o; o += align64(512 * 4);
-  L.hbuf = o; o += t->grad ? static_cast<size_t>(L.grid) * L.waves * TL_HBUF_FLOATS : 0;
+  L.hbuf = o; o += (t->grad || train) ? static_cast<size_t>(L.grid) * L.waves * TL_HBUF_FLOATS : 0;
   L.total = o;
   return L;
 }
-static int check_tilted(const sdeng_tilted* t) {
-  if (!t) return fail(SDENG_E_INVALID, "tilted_eval: null descriptor");
+// `who`: the entry point, for the messages; `train`: sdeng_tilted_vjp, where log_prob and grad may both be absent
+static int check_tilted(const sdeng_tilted* t, const char* who = "tilted_eval", bool train = false) {
+  if (!t) return fail(SDENG_E_INVALID, "%s: null descriptor", who);
   if (t->abi_version != SDENG_ABI_VERSION) return fail(SDENG_E_INVALID, "ABI version %d, library has %d", t->abi_version, SDENG_ABI_VERSION);
-  if (t->d < 1 || t->d > 128) return fail(SDENG_E_INVALID, "tilted_eval: d = %d outside [1, 128]", t->d);
-  if (t->k < 1 || t->k > TL_KMAX) return fail(SDENG_E_INVALID, "tilted_eval: k = %d components outside [1, %d]", t->k, TL_KMAX);
+  if (t->d < 1 || t->d > 128) return fail(SDENG_E_INVALID, "%s: d = %d outside [1, 128]", who, t->d);
+  if (t->k < 1 || t->k > TL_KMAX) return fail(SDENG_E_INVALID, "%s: k = %d components outside [1, %d]", who, t->k, TL_KMAX);
   if (t->M < 1 || t->n_times < 1 || t->rows_per_time < 1 || static_cast<long long>(t->n_times) * t->rows_per_time != t->M)
-    return fail(SDENG_E_INVALID, "tilted_eval: M = %d rows is not n_times * rows_per_time = %d * %d", t->M, t->n_times, t->rows_per_time);
-  if (static_cast<long long>(t->M) * t->d >= (1ll << 31)) return fail(SDENG_E_UNSUPPORTED, "tilted_eval: rows * d >= 2^31");
+    return fail(SDENG_E_INVALID, "%s: M = %d rows is not n_times * rows_per_time = %d * %d", who, t->M, t->n_times, t->rows_per_time);
+  if (static_cast<long long>(t->M) * t->d >= (1ll << 31)) return fail(SDENG_E_UNSUPPORTED, "%s: rows * d >= 2^31", who);
   if (t->num_layers != 6 || t->channels != TL_H)
-    return fail(SDENG_E_UNSUPPORTED, "tilted_eval: the kernel is built for FourierMLP(num_layers=6, channels=128), got num_layers=%d channels=%d",
+    return fail(SDENG_E_UNSUPPORTED, "%s: the kernel is built for FourierMLP(num_layers=6, channels=128), got num_layers=%d channels=%d", who,
                 t->num_layers, t->channels);
-  if (t->tilt_type != SDENG_TILT_DOT) return fail(SDENG_E_UNSUPPORTED, "tilted_eval: tilt_type 'dot' only (type %d given)", t->tilt_type);
-  if (t->use_scaling_factor) return fail(SDENG_E_UNSUPPORTED, "tilted_eval: use_scaling_factor (the DRL scaling argument) is not supported");
+  if (t->tilt_type != SDENG_TILT_DOT) return fail(SDENG_E_UNSUPPORTED, "%s: tilt_type 'dot' only (type %d given)", who, t->tilt_type);
+  if (t->use_scaling_factor) return fail(SDENG_E_UNSUPPORTED, "%s: use_scaling_factor (the DRL scaling argument) is not supported", who);
   const void* need[] = {t->x, t->tinfo, t->w_in, t->b_in, t->w_out, t->b_out, t->te_coeff, t->te_phase, t->te_w1, t->te_b1, t->te_w2, t->te_b2,
                         t->mean_gauss, t->var_gauss, t->weights, t->means, t->vars, t->w_h[0], t->w_h[1], t->w_h[2], t->w_h[3],
                         t->b_h[0], t->b_h[1], t->b_h[2], t->b_h[3]};
   for (const void* p : need)
-    if (!p) return fail(SDENG_E_INVALID, "tilted_eval: null pointer in the descriptor");
-  if (t->full_cov && !t->eigvecs) return fail(SDENG_E_INVALID, "tilted_eval: full_cov without eigvecs");
-  if (!t->log_prob && !t->grad) return fail(SDENG_E_INVALID, "tilted_eval: nothing to compute (log_prob and grad are both NULL)");
+    if (!p) return fail(SDENG_E_INVALID, "%s: null pointer in the descriptor", who);
+  if (t->full_cov && !t->eigvecs) return fail(SDENG_E_INVALID, "%s: full_cov without eigvecs", who);
+  if (!train && !t->log_prob && !t->grad) return fail(SDENG_E_INVALID, "%s: nothing to compute (log_prob and grad are both NULL)", who);
   return 0;
 }
 extern "C" size_t sdeng_tilted_eval_workspace_bytes(const sdeng_tilted* t) {
   if (check_tilted(t)) return 0;
   return tilted_layout(t).total * sizeof(float);
 }
-extern "C" int sdeng_tilted_eval(const sdeng_tilted* t, void* stream) {
+// the pack (unless reused) and the one launch of either entry point; `rows`: the training instantiation
+static int run_tilted(const sdeng_tilted* t, const TiltedRows* rows, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  SD_TRY(check_tilted(t));
-  const TiltedLayout L = tilted_layout(t);
+  const TiltedLayout L = tilted_layout(t, rows != nullptr);
   const size_t need = L.total * sizeof(float);
   if (!t->workspace || t->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", t->workspace_bytes, need);
   float* ws = static_cast<float*>(t->workspace);
@@ -1254,7 +1255,34 @@ extern "C" int sdeng_tilted_eval(const sdeng_tilted* t, void* stream) {
   a.M = t->M; a.B = t->rows_per_time; a.d = d; a.N = t->n_times; a.K = t->k; a.full = t->full_cov ? 1 : 0;
   a.use_st = t->use_s_t_scaling ? 1 : 0; a.ntiles = L.ntiles;
   a.x = t->x; a.tinfo = t->tinfo; a.pack = ws + L.pack; a.consts = ws + L.consts;
-  a.hbuf = t->grad ? ws + L.hbuf : nullptr; a.log_prob = t->log_prob; a.grad = t->grad; a.trash = ws + L.trash;
-  SD_HIP(sd_launch_tilted(a, tiles_exact(d), L.grid, L.waves, s));
+  a.hbuf = (t->grad || rows) ? ws + L.hbuf : nullptr; a.log_prob = t->log_prob; a.grad = t->grad; a.trash = ws + L.trash;
+  if (rows) SD_HIP(sd_launch_tilted_train(a, *rows, tiles_exact(d), L.grid, L.waves, s));
+  else SD_HIP(sd_launch_tilted(a, tiles_exact(d), L.grid, L.waves, s));
   return 0;
+}
+extern "C" int sdeng_tilted_eval(const sdeng_tilted* t, void* stream) {
+  SD_TRY(check_tilted(t));
+  return run_tilted(t, nullptr, stream);
+}
+static int check_tilted_rows(const sdeng_tilted_rows* r) {
+  if (!r) return fail(SDENG_E_INVALID, "tilted_vjp: null rows");
+  for (int l = 0; l < 5; ++l) {
+    if (!r->a[l]) return fail(SDENG_E_INVALID, "tilted_vjp: rows->a[%d] is NULL", l);
+    if (!r->d[l]) return fail(SDENG_E_INVALID, "tilted_vjp: rows->d[%d] is NULL", l);
+  }
+  if (!r->xs) return fail(SDENG_E_INVALID, "tilted_vjp: rows->xs is NULL");
+  if (!r->dv) return fail(SDENG_E_INVALID, "tilted_vjp: rows->dv is NULL");
+  return 0;
+}
+extern "C" size_t sdeng_tilted_vjp_workspace_bytes(const sdeng_tilted* t) {
+  if (check_tilted(t, "tilted_vjp", true)) return 0;
+  return tilted_layout(t, true).total * sizeof(float);
+}
+extern "C" int sdeng_tilted_vjp(const sdeng_tilted* t, const sdeng_tilted_rows* r, void* stream) {
+  SD_TRY(check_tilted(t, "tilted_vjp", true));
+  SD_TRY(check_tilted_rows(r));
+  TiltedRows rows;
+  for (int l = 0; l < 5; ++l) { rows.a[l] = r->a[l]; rows.d[l] = r->d[l]; }
+  rows.xs = r->xs; rows.dv = r->dv;
+  return run_tilted(t, &rows, stream);
 }

@@ -49,6 +49,14 @@ struct TiltedArgs {
   float* grad;          // [M, d] or nullptr
   float* trash;         // [512 * 4]
 };
+// per-row arrays of the training instantiation (TRAIN), row-major, row r as in TiltedArgs: everything the weight gradients of
+// E_r = -prior_lp_r + f_r <v_r, xs_r> need (sdeng_tilted_vjp, include/sdeng.h); the outer products are the caller's
+struct TiltedRows {
+  float* a[5];          // [M, 128] gelu(h_l), l = 0..4
+  float* d[5];          // [M, 128] f_r dh_l: dh_l the cotangent of h_l under <v, xs> (the backward pass of J^T xs)
+  float* xs;            // [M, d] the scaled state
+  float* dv;            // [M, d] f_r xs, the cotangent of v
+};
 
 // one matrix (or a column range of it) -> one image slot, its power-of-two scale (k_weight_scales' rule) and its scaled bias
 struct TiltedPackJob {
@@ -66,6 +74,7 @@ struct TiltedPackArgs {
 };
 int sd_launch_tilted_pack(const TiltedPackArgs& a, hipStream_t s);
 int sd_launch_tilted(const TiltedArgs& a, int NT, int grid, int waves, hipStream_t s);
+int sd_launch_tilted_train(const TiltedArgs& a, const TiltedRows& rows, int NT, int grid, int waves, hipStream_t s);
 inline int sd_tilted_waves(int ntiles) {  // waves per workgroup: as many as still leave a workgroup for every CU
   int w = 1;
   while (w < 8 && ntiles / (2 * w) >= 256) w *= 2;
@@ -142,6 +151,17 @@ SD_INLINE f32x4 tl_load_h(const float* slot, int layer, int t, int lane) {
   return *reinterpret_cast<const f32x4*>(slot + ((layer * TL_HT + t) * 64 + lane) * 4);
 }
 
+// one [M][128] array of the training mode, in the layout of store_h (grad_kernel.hpp): this lane's four channels of every tile in one
+// 16-byte store; a pad row (row >= M, or the rows of an idle wave) goes to the lane's dump slot.  `c` scales (the f_r of the cotangents).
+SD_INLINE void tl_store_row(float* dst, float* trash, uint32_t row, bool live, int g, const f32x4 (&v)[TL_HT]) {
+#pragma unroll
+  for (int t = 0; t < TL_HT; ++t) *reinterpret_cast<f32x4*>(live ? dst + static_cast<size_t>(row) * TL_H + 16 * t + 4 * g : trash) = v[t];
+}
+SD_INLINE void tl_store_row(float* dst, float* trash, uint32_t row, bool live, int g, const f32x4 (&v)[TL_HT], float c) {
+#pragma unroll
+  for (int t = 0; t < TL_HT; ++t) *reinterpret_cast<f32x4*>(live ? dst + static_cast<size_t>(row) * TL_H + 16 * t + 4 * g : trash) = v[t] * c;
+}
+
 // grad[row] += c * v on the live features (the running sum of the score lives in the output array between the phases of the kernel:
 // every lane re-reads only what it wrote itself)
 template <int NT>
@@ -155,8 +175,9 @@ SD_INLINE void tl_grad_axpy(float* grad, float* trash, uint32_t row, int d, bool
   }
 }
 
-template <int NT>
-__global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
+// TRAIN: the same walk, and the per-row arrays of TiltedRows on the way (the backward pass then runs whether or not a.grad is asked for)
+template <int NT, bool TRAIN>
+__global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a, const TiltedRows rw) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, threads = blockDim.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = threads >> 6;
@@ -169,6 +190,7 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
   float* trash = a.trash + tid * 4;
   float* slot = a.hbuf ? a.hbuf + static_cast<size_t>(blockIdx.x * nw + wave) * TL_HBUF_FLOATS : nullptr;
   const bool want_grad = a.grad != nullptr;  // uniform
+  const bool want_bwd = TRAIN || want_grad;  // the pre-activations are kept and the backward pass runs
   const int per_round = gridDim.x * nw;
   const int rounds = (a.ntiles + per_round - 1) / per_round;
   auto img = [&](int i) { return a.pack + static_cast<size_t>(i) * TL_SLOT; };
@@ -350,7 +372,8 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) act[t][r] = gelu_fast(h[t][r]);
       }
-      if (want_grad) tl_store_h(slot, 0, lane, h);
+      if (want_bwd) tl_store_h(slot, 0, lane, h);
+      if constexpr (TRAIN) tl_store_row(rw.a[0], trash, row, live, g, act);
     }
     // ---- four hidden layers ----
     for (int l = 0; l < 4; ++l) {
@@ -365,7 +388,8 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) act[t][r] = gelu_fast(h[t][r]);
         }
-        if (want_grad) tl_store_h(slot, l + 1, lane, h);
+        if (want_bwd) tl_store_h(slot, l + 1, lane, h);
+        if constexpr (TRAIN) tl_store_row(rw.a[l + 1], trash, row, live, g, act);
       }
     }
     // ---- output layer, tilt 'dot': base_lp = -<v, xs>, and the -v / c_i half of base_grad ----
@@ -373,6 +397,13 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
     if (active) {
       f32x4 xs[NT], rci[NT], v[NT];
       scaled_input(xs, rci);
+      if constexpr (TRAIN) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          store_quad(rw.xs, trash, row, a.d, live, t, g, xs[t]);
+          store_quad(rw.dv, trash, row, a.d, live, t, g, xs[t] * f);
+        }
+      }
       tl_bias<NT>(v, cs + TL_C_BOUT, g);
       tl_mm<TL_HT, NT>(act, v, lds, lane);
       float dot = 0.0f;
@@ -390,7 +421,7 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
       if (want_grad) tl_grad_axpy<NT>(a.grad, trash, row, a.d, live, g, -f, v);
     }
     // ---- backward: J^T xs, the other half of base_grad ----
-    if (want_grad) {
+    if (want_bwd) {
       f32x4 dh[TL_HT], gacc[TL_HT];
       tl_stage(lds, img(TL_WOUT_T), TL_HT * KBD, tid, threads);
       if (active) {
@@ -406,6 +437,7 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) dh[t][r] = (gacc[t][r] * back) * gelu_grad(hv[r]);
         }
+        if constexpr (TRAIN) tl_store_row(rw.d[4], trash, row, live, g, dh, f);
       }
       for (int l = 3; l >= 0; --l) {
         tl_stage(lds, img(TL_WH_T + l), TL_HT * TL_KBH, tid, threads);  // transpose of hidden layer l
@@ -420,10 +452,11 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) dh[t][r] = (gacc[t][r] * back) * gelu_grad(hv[r]);
           }
+          if constexpr (TRAIN) tl_store_row(rw.d[l], trash, row, live, g, dh, f);  // l = 0 included: the input layer's cotangent
         }
       }
-      tl_stage(lds, img(TL_WIN_T), NT * TL_KBH, tid, threads);
-      if (active) {
+      if (!TRAIN || want_grad) tl_stage(lds, img(TL_WIN_T), NT * TL_KBH, tid, threads);
+      if (active && (!TRAIN || want_grad)) {
         f32x4 xs[NT], rci[NT], jx[NT];
         scaled_input(xs, rci);
         const float sg = row_normalise<TL_HT>(dh), back = inv[TL_WIN_T] / sg;
@@ -440,8 +473,8 @@ __global__ void __launch_bounds__(512, 2) k_tilted_eval(const TiltedArgs a) {
   }
 }
 
-template <int NT>
-static int launch_tilted(const TiltedArgs& a, int grid, int waves, hipStream_t stream) {
-  return sd_launch_kernel(k_tilted_eval<NT>, grid, waves * 64, static_cast<size_t>(TL_SLOT) * sizeof(float), stream, a);
+template <int NT, bool TRAIN>
+static int launch_tilted(const TiltedArgs& a, const TiltedRows& rows, int grid, int waves, hipStream_t stream) {
+  return sd_launch_kernel(k_tilted_eval<NT, TRAIN>, grid, waves * 64, static_cast<size_t>(TL_SLOT) * sizeof(float), stream, a, rows);
 }
 #endif

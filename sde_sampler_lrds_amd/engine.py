@@ -1262,7 +1262,13 @@ def tilted_eval(net, t, x: torch.Tensor, want_grad=True, want_logp=True, per_row
     rows as N = M times of one row each whatever ``t`` holds (same results; for tests)."""
     if tilted_needs_param_grad(net):
         raise UnsupportedByEngine("tilted_eval computes no gradient with respect to the net's parameters: call it under torch.no_grad() "
-                                  "or with requires_grad_(False) parameters (training an EBM is not on the HIP path)")
+                                  "or with requires_grad_(False) parameters; first-order parameter gradients of net.energy / "
+                                  "net.unnorm_log_prob are the opt-in net.param_grads = True (tilted_vjp), the score's are not on the HIP path")
+    return _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, False)[:2]
+
+
+def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
+    """The one launch behind tilted_eval (sdeng_tilted_eval) and tilted_vjp (``train``: sdeng_tilted_vjp, with the per-row arrays)."""
     require_gpu(x)
     lib = L.lib()
     device, keep = x.device, []
@@ -1286,9 +1292,21 @@ def tilted_eval(net, t, x: torch.Tensor, want_grad=True, want_logp=True, per_row
     logp = torch.empty(M, dtype=torch.float32, device=device) if want_logp else None
     grad = torch.empty(M, dim, dtype=torch.float32, device=device) if want_grad else None
     d.log_prob, d.grad = (logp.data_ptr() if want_logp else None), (grad.data_ptr() if want_grad else None)
-    need = lib.sdeng_tilted_eval_workspace_bytes(C.byref(d))
+    arrays, rows = None, None
+    if train:
+        hid, io = torch.empty(10, M, 128, dtype=torch.float32, device=device), torch.empty(2, M, dim, dtype=torch.float32, device=device)
+        arrays = {"a": list(hid[:5]), "d": list(hid[5:]), "xs": io[0], "dv": io[1], "a_all": hid[:5], "d_all": hid[5:]}
+        rows = L.TiltedRows()
+        for l in range(5):
+            rows.a[l], rows.d[l] = arrays["a"][l].data_ptr(), arrays["d"][l].data_ptr()
+        rows.xs, rows.dv = io[0].data_ptr(), io[1].data_ptr()
+        launch = lambda: lib.sdeng_tilted_vjp(C.byref(d), C.byref(rows), _stream_ptr(device))  # noqa: E731
+        need = lib.sdeng_tilted_vjp_workspace_bytes(C.byref(d))
+    else:
+        launch = lambda: lib.sdeng_tilted_eval(C.byref(d), _stream_ptr(device))  # noqa: E731
+        need = lib.sdeng_tilted_eval_workspace_bytes(C.byref(d))
     if need == 0:
-        rc = lib.sdeng_tilted_eval(C.byref(d), _stream_ptr(device))  # the descriptor is rejected: fetch the code and the reason
+        rc = launch()  # the descriptor is rejected: fetch the code and the reason
         if rc == L.E_UNSUPPORTED:
             raise UnsupportedByEngine(lib.sdeng_last_error().decode())
         L.check(rc)
@@ -1300,8 +1318,79 @@ def tilted_eval(net, t, x: torch.Tensor, want_grad=True, want_logp=True, per_row
         ws = torch.empty(need, dtype=torch.uint8, device=device)
         _TILTED_PACKS[net] = (versions, ws)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    rc = lib.sdeng_tilted_eval(C.byref(d), _stream_ptr(device))
+    rc = launch()
     if rc == L.E_UNSUPPORTED:
         raise UnsupportedByEngine(lib.sdeng_last_error().decode())
     L.check(rc)
-    return logp, grad
+    return logp, grad, arrays, (n_times, B, tdev[:, 0])
+
+
+def tilted_vjp(net, t, x: torch.Tensor, want_grad=False, per_row_times=False):
+    """sdeng_tilted_vjp: one launch of the training instantiation of the tilted kernel at the rows (t, x).  Returns (log_prob [M],
+    grad [M,d] or None, arrays, (N, B, t_unique [N])): the evaluation of ``tilted_eval`` (same bits) and the per-row arrays
+    ``tilted_param_grads`` turns into the gradient of any function of the energies E_r = -log_prob_r with respect to the net's
+    parameters -- ``arrays`` = {"a": [gelu(h_l)] * 5, "d": [f dh_l] * 5, "xs", "dv"} (include/sdeng.h; "a_all" / "d_all": the same
+    memory as [5,M,128] blocks).  Pack cache and time handling
+    are tilted_eval's; nothing here is recorded by autograd (``tilted_energy`` is the differentiable entry)."""
+    with torch.no_grad():
+        return _tilted_launch(net, t, x.detach(), want_grad, True, per_row_times, True)
+
+
+def tilted_param_grads(net, arrays, cot, N, B, t_unique):
+    """Per-row arrays of ``tilted_vjp`` and the cotangent ``cot`` [M] of the energies (dL/dE_r) -> {parameter: gradient} for the
+    FourierMLP of a tilted potential (include/sdeng.h: sdeng_tilted_vjp).  Plain torch on whatever device and dtype the arrays have: the
+    products are batched over the N times and summed, as in ``losses.training.vjp_param_grads``; the time embedding (2 layers on N rows)
+    is differentiated by torch with the cotangent sum_b d[0]."""
+    base = net.base_model
+    c = cot.detach().reshape(-1, 1).to(arrays["xs"].dtype)
+    # the five [M,128] arrays of a kind as one [5,M,128] block (tilted_vjp allocates them so: "a_all", "d_all"): one scaling, one column sum
+    # and one batched product for the four hidden layers instead of one each -- at the trainer's shapes this part is bound by launches
+    a = arrays["a_all"] if "a_all" in arrays else torch.stack(list(arrays["a"]))
+    d = c * (arrays["d_all"] if "d_all" in arrays else torch.stack(list(arrays["d"])))
+    dv, H = c * arrays["dv"], a.shape[-1]
+
+    def outer(dl, act):
+        return torch.bmm(dl.view(N, B, -1).transpose(1, 2), act.view(N, B, -1)).sum(0)
+    db = d.sum(1)
+    dw = torch.bmm(d[1:].reshape(4 * N, B, H).transpose(1, 2), a[:4].reshape(4 * N, B, H)).view(4, N, H, H).sum(1)
+    grads = {base.out_layer.weight: outer(dv, a[4]), base.out_layer.bias: dv.sum(0),
+             base.input_embed.weight: outer(d[0], arrays["xs"]), base.input_embed.bias: db[0]}
+    for l, layer in enumerate(list(base.hidden_layer)[:4], start=1):
+        grads[layer.weight], grads[layer.bias] = dw[l - 1], db[l]
+    te_params = [p for p in base.timestep_embed.parameters() if p.requires_grad]
+    if te_params:
+        with torch.enable_grad():
+            e = base.timestep_embed(t_unique.view(-1, 1).to(c.dtype))
+            te_grads = torch.autograd.grad(e, te_params, grad_outputs=d[0].view(N, B, H).sum(1), allow_unused=True)
+        grads.update({p: g for p, g in zip(te_params, te_grads) if g is not None})
+    return grads
+
+
+class _TiltedEnergy(torch.autograd.Function):
+    """E = net.energy(t, x) with a first-order graph: forward is one tilted_vjp launch, backward the products of tilted_param_grads
+    (and -grad_output * score for x).  The arrays stay on the context, so backward may run again (retain_graph, accumulation)."""
+
+    @staticmethod
+    def forward(ctx, net, t, x, *params):
+        need_x = ctx.needs_input_grad[2]
+        logp, score, arrays, layout = tilted_vjp(net, t, x, want_grad=need_x)
+        ctx.net, ctx.arrays, ctx.layout, ctx.score, ctx.params = net, arrays, layout, score, params
+        ctx.versions = [(p, p._version) for p in net.parameters()]
+        return -logp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if any(p._version != v for p, v in ctx.versions):
+            raise RuntimeError("tilted_energy: a parameter of the net was modified in place between the forward pass and backward "
+                               "(the per-row arrays are those of the old parameters)")
+        grads = tilted_param_grads(ctx.net, ctx.arrays, g, *ctx.layout) if any(ctx.needs_input_grad[3:]) else {}
+        gx = -g.reshape(-1, 1) * ctx.score if ctx.needs_input_grad[2] else None
+        return (None, None, gx) + tuple(grads.get(p) if need else None for p, need in zip(ctx.params, ctx.needs_input_grad[3:]))
+
+
+def tilted_energy(net, t, x):
+    """``net.energy(t, x)`` [M] carrying a graph to the net's trainable parameters and to ``x`` (first order), from one
+    ``sdeng_tilted_vjp`` launch: what ``GMMTitledPotential`` returns with ``param_grads = True``."""
+    params = [p for p in net.base_model.parameters() if p.requires_grad]
+    return _TiltedEnergy.apply(net, t, x, *params)

@@ -118,8 +118,15 @@ class GMMTitledPotential(Module):
 
     Every evaluation -- ``unnorm_log_prob``, ``unnorm_log_prob_and_grad``, ``energy``, ``forward`` (the score) -- is ONE
     ``engine.tilted_eval`` launch on the GPU; nothing is differentiated by autograd, so the results carry no graph.  A call that would
-    need gradients with respect to the net's parameters (grad mode with parameters that require grad: the EBM trainer) raises
-    ``UnsupportedByEngine``: there is no torch fallback.  ``scaling_factor`` (DRL) is not supported."""
+    need gradients with respect to the net's parameters (grad mode with parameters that require grad) raises ``UnsupportedByEngine``:
+    there is no torch fallback.  ``scaling_factor`` (DRL) is not supported.
+
+    ``param_grads = True`` (off by default; ``MaximumLikelihoodEBM.train`` switches it on for its duration) lets ``energy`` and
+    ``unnorm_log_prob`` carry a first-order graph in grad mode -- to the net's trainable parameters and to ``x`` -- from one
+    ``engine.tilted_vjp`` launch (``engine.tilted_energy``).  ``unnorm_log_prob_and_grad`` and ``forward`` keep raising with trainable
+    parameters: differentiating the score is second order."""
+
+    param_grads = False
 
     def __init__(self, base_model, sde, weights, means, variances, t_limit=0.0, use_s_t_scaling=False, tilt_type="dot",
                  use_scaling_factor=False):
@@ -174,10 +181,21 @@ class GMMTitledPotential(Module):
             raise E.UnsupportedByEngine("tilted potentials: scaling_factor / use_scaling_factor (DRL) is not on the HIP path")
         return E.tilted_eval(self, t, x, want_grad=want_grad)
 
+    def _with_graph(self, x):
+        from .. import engine as E
+        return self.param_grads and torch.is_grad_enabled() and (E.tilted_needs_param_grad(self) or (torch.is_tensor(x) and x.requires_grad))
+
     def unnorm_log_prob(self, t, x, scaling_factor=1.0):
+        if self._with_graph(x):
+            return -self.energy(t, x, scaling_factor=scaling_factor)
         return self._eval(t, x, scaling_factor, False)[0]
 
     def energy(self, t, x, scaling_factor=1.0):
+        if self._with_graph(x):
+            from .. import engine as E
+            if self.use_scaling_factor or not (isinstance(scaling_factor, (int, float)) and float(scaling_factor) == 1.0):
+                raise E.UnsupportedByEngine("tilted potentials: scaling_factor / use_scaling_factor (DRL) is not on the HIP path")
+            return E.tilted_energy(self, t, x)
         return -self.unnorm_log_prob(t, x, scaling_factor=scaling_factor)
 
     def unnorm_log_prob_and_grad(self, t, x, scaling_factor=1.0, retain_graph=False):
