@@ -28,7 +28,7 @@ def hip_tempered_log_prob_and_grads(target, prior):
     return fn
 
 
-# Local moves of a level as ONE HIP launch (csrc/prep_kernels.hip k_langevin_moves) when the annealing path is
+# Local moves of a level as ONE HIP launch (csrc/prep_kernels.hip k_chain_moves) when the annealing path is
 # hip_tempered_log_prob_and_grads and the moves are not preconditioned.  NATIVE_NOISE = False: the random numbers still come from torch's
 # generator, drawn in the reference's order (the chains are then the reference's chains, tests/golden/smc_*.npz, re_*.npz);
 # True: counter-based draws inside the kernel (seeded by NATIVE_SEED and a per-call counter).
@@ -44,19 +44,14 @@ def _native_pair(log_prob_and_grads, x, precond):
 
 
 def _native_run(pair, t, x, lp, grad, step, n_moves, keep_from, use_ula, target_acceptance, want_samples=True):
-    """n_moves local moves of all chains; x / lp / grad / step ([B,d], [B], [B,d], [B] contiguous) are updated in place."""
+    """n_moves local moves of all chains; x / lp / grad / step ([B,d], [B], [B,d], [B] contiguous) are updated in place.  ``grad is None``:
+    random-walk Metropolis moves on ``pair[0]`` alone (no ``t``, no ULA); otherwise Langevin moves on the path between the pair."""
     _native_calls[0] += 1
-    return E.langevin_moves(pair[0], pair[1], x, lp, grad, step, n_moves, t=t, keep_from=keep_from, unadjusted=use_ula,
-                            target_acceptance=target_acceptance if not use_ula else 0.0, noise="philox" if NATIVE_NOISE else "torch",
-                            seed=(NATIVE_SEED + 0x9E3779B97F4A7C15 * _native_calls[0]) & 0xFFFFFFFFFFFFFFFF, want_samples=want_samples)
-
-
-def _native_rwmh(target, x, lp, step, n_moves, keep_from, target_acceptance):
-    """n_moves random-walk Metropolis moves of all chains (csrc/prep_kernels.hip k_rwmh_moves); x / lp / step ([B,d], [B], [B] contiguous) are
-    updated in place.  Random numbers as configured above, like the Langevin moves."""
-    _native_calls[0] += 1
-    return E.rwmh_moves(target, x, lp, step, n_moves, keep_from=keep_from, target_acceptance=target_acceptance,
-                        noise="philox" if NATIVE_NOISE else "torch", seed=(NATIVE_SEED + 0x9E3779B97F4A7C15 * _native_calls[0]) & 0xFFFFFFFFFFFFFFFF)
+    kw = dict(keep_from=keep_from, target_acceptance=target_acceptance if not use_ula else 0.0, noise="philox" if NATIVE_NOISE else "torch",
+              seed=(NATIVE_SEED + 0x9E3779B97F4A7C15 * _native_calls[0]) & 0xFFFFFFFFFFFFFFFF, want_samples=want_samples)
+    if grad is None:
+        return E.rwmh_moves(pair[0], x, lp, step, n_moves, **kw)
+    return E.langevin_moves(pair[0], pair[1], x, lp, grad, step, n_moves, t=t, unadjusted=use_ula, **kw)
 
 
 def _pmul(mat, v):
@@ -236,43 +231,41 @@ def re_sampler(x_init, times, log_prob_and_grads, swap_frequency, n_warmup_mcmc_
     if native is not None:
         x, lp, grad = x.contiguous().clone(), lp.contiguous().clone(), grad.contiguous().clone()
         step_shape, step = step.shape, step.to(torch.float32).reshape(-1).expand(x.shape[0]).contiguous().clone()
+
+    def store(it, y):
+        if it >= n_warmup_mcmc_steps:
+            samples[:, it - n_warmup_mcmc_steps] = y.reshape((-1, B, *data_shape))
+        if verbose and it % 50 == 0:
+            print(f"re step {it}: swap acc {float(mean_swap_acc):.3f}")
+
     it = 0
-    while native is not None and it < total:
-        if it % swap_frequency == 0:
-            pr = pairs[(it // swap_frequency) % 2]
-            xs_, lps_, gs_, mean_swap_acc = re_step(x.view((-1, B, *data_shape)), lp.view((-1, B)), grad.view((-1, B, *data_shape)), batched,
-                                                    times, pr[:, 0], pr[:, 1], B, data_shape, ones)
-            x, grad, lp = xs_.reshape((-1, *data_shape)).contiguous(), gs_.reshape((-1, *data_shape)).contiguous(), lps_.flatten().contiguous()
-            if it >= n_warmup_mcmc_steps:
-                samples[:, it - n_warmup_mcmc_steps] = x.reshape((-1, B, *data_shape))
-            it += 1
-            continue
-        run = min(swap_frequency - it % swap_frequency, total - it) if swap_frequency > 0 else total - it  # local moves up to the next swap step
-        keep = max(0, n_warmup_mcmc_steps - it)
-        got, _, last = _native_run(native, t_flat.reshape(-1), x, lp, grad, step, run, min(keep, run), use_ula, target_acceptance, want_samples=keep < run)
-        if keep < run:
-            first = it + keep - n_warmup_mcmc_steps
-            samples[:, first:first + run - keep] = got.view(run - keep, n_levels, B, *data_shape).transpose(0, 1)
-        if last is not None:
-            mean_local_accs = last.view((-1, B)).mean(dim=-1)
-        it += run
-    if native is not None:
-        step = step.view(step_shape)
-    for it in range(0 if native is None else total, total):
+    while it < total:
         if it % swap_frequency == 0:
             pr = pairs[(it // swap_frequency) % 2]
             x, lp, grad, mean_swap_acc = re_step(x.view((-1, B, *data_shape)), lp.view((-1, B)), grad.view((-1, B, *data_shape)), batched,
                                                  times, pr[:, 0], pr[:, 1], B, data_shape, ones)
-            x, grad, lp = x.view((-1, *data_shape)), grad.view((-1, *data_shape)), lp.flatten()
+            x, grad, lp = x.reshape((-1, *data_shape)).contiguous(), grad.reshape((-1, *data_shape)).contiguous(), lp.flatten().contiguous()
             pgrad = move.pgrad(grad)
-        else:
+            store(it, x)
+            it += 1
+        elif native is None:  # one host move
             x, lp, grad, pgrad, step, log_acc = move(x, lp, grad, pgrad, step)
             if log_acc is not None:
                 mean_local_accs = torch.exp(torch.minimum(torch.zeros_like(log_acc), log_acc)).view((-1, B)).mean(dim=-1)
-        if it >= n_warmup_mcmc_steps:
-            samples[:, it - n_warmup_mcmc_steps] = x.reshape((-1, B, *data_shape)).clone()
-        if verbose and it % 50 == 0:
-            print(f"re step {it}: swap acc {float(mean_swap_acc):.3f}")
+            store(it, x)
+            it += 1
+        else:  # the local moves up to the next swap step in one launch
+            run = min(swap_frequency - it % swap_frequency, total - it)
+            keep = max(0, n_warmup_mcmc_steps - it)
+            got, _, last = _native_run(native, t_flat.reshape(-1), x, lp, grad, step, run, min(keep, run), use_ula, target_acceptance, want_samples=keep < run)
+            if keep < run:
+                first = it + keep - n_warmup_mcmc_steps
+                samples[:, first:first + run - keep] = got.view(run - keep, n_levels, B, *data_shape).transpose(0, 1)
+            if last is not None:
+                mean_local_accs = last.view((-1, B)).mean(dim=-1)
+            it += run
+    if native is not None:
+        step = step.view(step_shape)
     diags = {"swap_acc": mean_swap_acc}
     if not use_ula:
         diags["local_acc"] = mean_local_accs

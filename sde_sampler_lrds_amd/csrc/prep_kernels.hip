@@ -753,10 +753,13 @@ __global__ void __launch_bounds__(SD_EVAL_THREADS) k_dist_eval(DistEvalArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Langevin moves of the annealed samplers: one thread per chain, the chain's state / gradient / proposal rows in LDS, all K
-// moves of a level in ONE launch -- the reference (and the host composition this replaces) spends ~30 small launches per move.
+// Local moves of the annealed samplers and of the learned-reference data set: one thread per chain, the chain's rows in LDS,
+// all K moves of a level in ONE launch -- the reference (and the host composition this replaces) spends ~30 small launches per move.
+// One skeleton, two instantiations: Langevin (MALA / ULA, the runtime flag a.ula) and random-walk Metropolis, which has no gradient, no
+// score call and no prior.  What differs per move is marked `if constexpr`; everything else is written once.
 // ------------------------------------------------------------------------------------------------
-#define SD_MOVE_ROWS 5  // x, grad, proposal, gradient at the proposal, scratch score row
+// LDS rows per chain.  Langevin: x, grad, proposal, gradient at the proposal, scratch score row.  RWMH: x, proposal.
+constexpr int sd_move_rows(int move) { return move == SD_MOVE_RWMH ? 2 : 5; }
 __device__ inline void tempered_eval(const MovesArgs& a, float w, const float* y, float* g_out, float* tmp, float& lp_out) {
   const bool both = a.prior.ds.kind != SDENG_DIST_NONE;
   const float lp1 = dist_logp_row(a.target, y);
@@ -771,58 +774,75 @@ __device__ inline void tempered_eval(const MovesArgs& a, float w, const float* y
   for (int f = 0; f < a.d; ++f) g_out[f] = (1.0f - w) * tmp[f] + w * g_out[f];
 }
 
-__global__ void __launch_bounds__(64) k_langevin_moves(MovesArgs a, int chains_per_block) {
+// Non-finite log-densities keep their IEEE meaning in the RWMH move, which is the reference's on the checkerboard: a proposal outside every
+// square has log_acc = -inf (rejected, the step shrinks); a chain that starts outside (lp = -inf) has +inf for a proposal inside (accepted,
+// the step grows) and NaN for one outside (rejected, both step comparisons are false).
+template <int MOVE>
+__global__ void __launch_bounds__(64) k_chain_moves(MovesArgs a, int chains_per_block) {
+  constexpr bool LANGEVIN = MOVE == SD_MOVE_LANGEVIN;
+  constexpr uint32_t Z_STREAM = LANGEVIN ? 2u : 6u, U_STREAM = Z_STREAM + 1u;  // Philox stream ids of the normals and the uniforms
   extern __shared__ float sh[];
   const int tid = threadIdx.x, d = a.d, stride = d | 1;
   const int chain = blockIdx.x * chains_per_block + tid;
   if (tid >= chains_per_block || chain >= a.B) return;  // (no barriers below: a chain is one thread)
-  float* xr = sh + (tid * SD_MOVE_ROWS + 0) * stride;
-  float* gr = xr + stride;
-  float* pr = gr + stride;
+  const bool ula = LANGEVIN && a.ula;
+  float* xr = sh + (tid * sd_move_rows(MOVE) + 0) * stride;
+  float* gr = xr + stride;  // (gr, gp and tmp: Langevin only)
+  float* pr = xr + (LANGEVIN ? 2 : 1) * stride;
   float* gp = pr + stride;
   float* tmp = gp + stride;
   for (int f = 0; f < d; ++f) {
     xr[f] = a.x[static_cast<size_t>(chain) * d + f];
-    gr[f] = a.grad[static_cast<size_t>(chain) * d + f];
+    if constexpr (LANGEVIN) gr[f] = a.grad[static_cast<size_t>(chain) * d + f];
   }
   float lp = a.lp[chain], step = a.step[chain], acc = 0.0f, last = 1.0f;
-  const float w = a.t ? a.t[chain] : 1.0f;
+  const float w = LANGEVIN && a.t ? a.t[chain] : 1.0f;
   const uint32_t cidx = static_cast<uint32_t>(a.chain0 + chain);
   const float log_target = a.target_acc > 0.0f ? logf(a.target_acc) : 0.0f;
   for (int m = 0; m < a.K; ++m) {
+    // proposal.  Langevin: sample_multivariate_normal_diag(mean = y + h grad, variance = 2 h)  (mcmc.py:19-21, :97-99);
+    // RWMH: y + step_size * randn_like(y) -- the standard deviation is the step itself (mcmc.py:279)
     const float sd = sqrtf(2.0f * step);
-    // proposal: sample_multivariate_normal_diag(mean = y + h grad, variance = 2 h)  (mcmc.py:19-21, :97-99)
     for (int f0 = 0; f0 < d; f0 += 4) {
       f32x4 z;
       if (a.z) {
         for (int r = 0; r < 4; ++r) z[r] = f0 + r < d ? a.z[(static_cast<size_t>(m) * a.B + chain) * d + f0 + r] : 0.0f;
       } else {
-        z = philox_normal4(cidx, static_cast<uint32_t>(m), static_cast<uint32_t>(f0 >> 2), 2u, a.seed_lo, a.seed_hi);
+        z = philox_normal4(cidx, static_cast<uint32_t>(m), static_cast<uint32_t>(f0 >> 2), Z_STREAM, a.seed_lo, a.seed_hi);
       }
-      for (int r = 0; r < 4 && f0 + r < d; ++r) pr[f0 + r] = sd * z[r] + (xr[f0 + r] + step * gr[f0 + r]);
+      for (int r = 0; r < 4 && f0 + r < d; ++r) {
+        if constexpr (LANGEVIN) pr[f0 + r] = sd * z[r] + (xr[f0 + r] + step * gr[f0 + r]);
+        else pr[f0 + r] = xr[f0 + r] + step * z[r];
+      }
     }
-    float lp_p;
-    tempered_eval(a, w, pr, gp, tmp, lp_p);
-    bool accept = true;
-    float log_acc = 0.0f;
-    if (!a.ula) {
-      // log q(prop | y) and log q(y | prop), unnormalised: -0.5 sum (samples - mean)^2 / variance  (mcmc.py:24-31)
-      float qf = 0.0f, qb = 0.0f;
-      for (int f = 0; f < d; ++f) {
-        const float df = pr[f] - (xr[f] + step * gr[f]);
-        const float db = xr[f] - (pr[f] + step * gp[f]);
-        qf += df * df;
-        qb += db * db;
+    float lp_p, log_acc = 0.0f;
+    if constexpr (LANGEVIN) {
+      tempered_eval(a, w, pr, gp, tmp, lp_p);
+      if (!ula) {
+        // log q(prop | y) and log q(y | prop), unnormalised: -0.5 sum (samples - mean)^2 / variance  (mcmc.py:24-31)
+        float qf = 0.0f, qb = 0.0f;
+        for (int f = 0; f < d; ++f) {
+          const float df = pr[f] - (xr[f] + step * gr[f]);
+          const float db = xr[f] - (pr[f] + step * gp[f]);
+          qf += df * df;
+          qb += db * db;
+        }
+        const float var = 2.0f * step;
+        const float joint_prop = lp_p - (-0.5f * qf) / var, joint_orig = lp - (-0.5f * qb) / var;
+        log_acc = joint_prop - joint_orig;
       }
-      const float var = 2.0f * step;
-      const float joint_prop = lp_p - (-0.5f * qf) / var, joint_orig = lp - (-0.5f * qb) / var;
-      log_acc = joint_prop - joint_orig;
+    } else {
+      lp_p = dist_logp_row(a.target, pr);
+      log_acc = lp_p - lp;  // (mcmc.py:283)
+    }
+    bool accept = true;
+    if (!ula) {
       float uu;
       if (a.u) {
         uu = a.u[static_cast<size_t>(m) * a.B + chain];
       } else {
         uint32_t r4[4];
-        philox4x32_10(cidx, 0u, static_cast<uint32_t>(m), 3u, a.seed_lo, a.seed_hi, r4);
+        philox4x32_10(cidx, 0u, static_cast<uint32_t>(m), U_STREAM, a.seed_lo, a.seed_hi, r4);
         uu = u01(r4[0]);
       }
       accept = logf(uu) < log_acc;
@@ -830,17 +850,17 @@ __global__ void __launch_bounds__(64) k_langevin_moves(MovesArgs a, int chains_p
     if (accept) {
       for (int f = 0; f < d; ++f) {
         xr[f] = pr[f];
-        gr[f] = gp[f];
+        if constexpr (LANGEVIN) gr[f] = gp[f];
       }
       lp = lp_p;
     }
-    if (!a.ula && a.target_acc > 0.0f) {  // heuristics_step_size (mcmc.py:55-74), per chain
+    if (!ula && a.target_acc > 0.0f) {  // heuristics_step_size (mcmc.py:55-74), per chain
       if (log_acc - log_target > 0.04879016416943205f) step = step * 1.01f;        // log1p(0.05)
       if (log_target - log_acc > 0.05129329438755058f) step = step / 1.01f;        // -log1p(-0.05)
     }
-    if (!a.ula) last = expf(fminf(0.0f, log_acc));
+    if (!ula) last = expf(fminf(0.0f, log_acc));
     if (m >= a.keep_from) {
-      if (!a.ula) acc += last;
+      if (!ula) acc += last;
       if (a.samples) {
         float* dst = a.samples + (static_cast<size_t>(m - a.keep_from) * a.B + chain) * d;
         for (int f = 0; f < d; ++f) dst[f] = xr[f];
@@ -849,70 +869,8 @@ __global__ void __launch_bounds__(64) k_langevin_moves(MovesArgs a, int chains_p
   }
   for (int f = 0; f < d; ++f) {
     a.x[static_cast<size_t>(chain) * d + f] = xr[f];
-    a.grad[static_cast<size_t>(chain) * d + f] = gr[f];
+    if constexpr (LANGEVIN) a.grad[static_cast<size_t>(chain) * d + f] = gr[f];
   }
-  a.lp[chain] = lp;
-  a.step[chain] = step;
-  if (a.acc_sum) a.acc_sum[chain] = acc;
-  if (a.acc_last) a.acc_last[chain] = last;
-}
-
-// Random-walk Metropolis moves of the learned-reference data set (experiments/benchmark_utils.py:281-290 -> rwmh_step, additions/mcmc.py:
-// 256-293, with heuristics_step_size of :54-72): the layout of k_langevin_moves -- one thread per chain, no barriers -- with two LDS rows per
-// chain (state, proposal), no gradient and no score call.  Non-finite log-densities keep their IEEE meaning, which is the reference's on the
-// checkerboard: a proposal outside every square has log_acc = -inf (rejected, the step shrinks); a chain that starts outside (lp = -inf)
-// has +inf for a proposal inside (accepted, the step grows) and NaN for one outside (rejected, both step comparisons are false).
-#define SD_RWMH_ROWS 2  // x, proposal
-__global__ void __launch_bounds__(64) k_rwmh_moves(RwmhArgs a, int chains_per_block) {
-  extern __shared__ float sh[];
-  const int tid = threadIdx.x, d = a.d, stride = d | 1;
-  const int chain = blockIdx.x * chains_per_block + tid;
-  if (tid >= chains_per_block || chain >= a.B) return;  // (no barriers below: a chain is one thread)
-  float* xr = sh + (tid * SD_RWMH_ROWS + 0) * stride;
-  float* pr = xr + stride;
-  for (int f = 0; f < d; ++f) xr[f] = a.x[static_cast<size_t>(chain) * d + f];
-  float lp = a.lp[chain], step = a.step[chain], acc = 0.0f, last = 1.0f;
-  const uint32_t cidx = static_cast<uint32_t>(a.chain0 + chain);
-  const float log_target = a.target_acc > 0.0f ? logf(a.target_acc) : 0.0f;
-  for (int m = 0; m < a.K; ++m) {
-    // proposal: y + step_size * randn_like(y) -- the standard deviation is the step itself (mcmc.py:279)
-    for (int f0 = 0; f0 < d; f0 += 4) {
-      f32x4 z;
-      if (a.z) {
-        for (int r = 0; r < 4; ++r) z[r] = f0 + r < d ? a.z[(static_cast<size_t>(m) * a.B + chain) * d + f0 + r] : 0.0f;
-      } else {
-        z = philox_normal4(cidx, static_cast<uint32_t>(m), static_cast<uint32_t>(f0 >> 2), 6u, a.seed_lo, a.seed_hi);
-      }
-      for (int r = 0; r < 4 && f0 + r < d; ++r) pr[f0 + r] = xr[f0 + r] + step * z[r];
-    }
-    const float lp_p = dist_logp_row(a.target, pr);
-    const float log_acc = lp_p - lp;  // (mcmc.py:283)
-    float uu;
-    if (a.u) {
-      uu = a.u[static_cast<size_t>(m) * a.B + chain];
-    } else {
-      uint32_t r4[4];
-      philox4x32_10(cidx, 0u, static_cast<uint32_t>(m), 7u, a.seed_lo, a.seed_hi, r4);
-      uu = u01(r4[0]);
-    }
-    if (logf(uu) < log_acc) {
-      for (int f = 0; f < d; ++f) xr[f] = pr[f];
-      lp = lp_p;
-    }
-    if (a.target_acc > 0.0f) {  // heuristics_step_size (mcmc.py:54-72), per chain
-      if (log_acc - log_target > 0.04879016416943205f) step = step * 1.01f;        // log1p(0.05)
-      if (log_target - log_acc > 0.05129329438755058f) step = step / 1.01f;        // -log1p(-0.05)
-    }
-    last = expf(fminf(0.0f, log_acc));
-    if (m >= a.keep_from) {
-      acc += last;
-      if (a.samples) {
-        float* dst = a.samples + (static_cast<size_t>(m - a.keep_from) * a.B + chain) * d;
-        for (int f = 0; f < d; ++f) dst[f] = xr[f];
-      }
-    }
-  }
-  for (int f = 0; f < d; ++f) a.x[static_cast<size_t>(chain) * d + f] = xr[f];
   a.lp[chain] = lp;
   a.step[chain] = step;
   if (a.acc_sum) a.acc_sum[chain] = acc;
@@ -1136,16 +1094,13 @@ int sd_launch_dist_eval(const DistEvalArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_dist_eval, dim3((a.B + SD_EVAL_ROWS - 1) / SD_EVAL_ROWS), dim3(SD_EVAL_THREADS), (SD_EVAL_ROWS * (a.d | 1) + SD_EVAL_RED_FLOATS) * sizeof(float), s, a);
   return static_cast<int>(hipGetLastError());
 }
-int sd_launch_moves(const MovesArgs& a, hipStream_t s) {
-  const int stride = a.d | 1;
+int sd_launch_moves(const MovesArgs& a, int move, hipStream_t s) {
+  const size_t row_bytes = static_cast<size_t>(sd_move_rows(move)) * (a.d | 1) * sizeof(float);
   int cpb = 64;
-  while (cpb > 8 && static_cast<size_t>(cpb) * SD_MOVE_ROWS * stride * sizeof(float) > 150 * 1024) cpb /= 2;  // d > ~115: 32 chains per block
-  const size_t lds = static_cast<size_t>(cpb) * SD_MOVE_ROWS * stride * sizeof(float);
-  return sd_launch_kernel(k_langevin_moves, (a.B + cpb - 1) / cpb, 64, lds, s, a, cpb);
-}
-int sd_launch_rwmh(const RwmhArgs& a, hipStream_t s) {
-  const size_t lds = static_cast<size_t>(64) * SD_RWMH_ROWS * (a.d | 1) * sizeof(float);  // d <= 255: at most 128 KiB
-  return sd_launch_kernel(k_rwmh_moves, (a.B + 63) / 64, 64, lds, s, a, 64);
+  // Langevin, d > ~115: 32 chains per block (d > ~230: 16).  RWMH never halves: d <= 255 is at most 128 KiB at 64 chains.
+  while (cpb > 8 && cpb * row_bytes > 150 * 1024) cpb /= 2;
+  return sd_launch_kernel(move == SD_MOVE_RWMH ? k_chain_moves<SD_MOVE_RWMH> : k_chain_moves<SD_MOVE_LANGEVIN>, (a.B + cpb - 1) / cpb, 64,
+                          cpb * row_bytes, s, a, cpb);
 }
 int sd_launch_terminal(const TerminalArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_terminal, dim3((a.B + SD_EVAL_ROWS - 1) / SD_EVAL_ROWS), dim3(SD_EVAL_THREADS), (SD_EVAL_ROWS * (a.d | 1) + SD_EVAL_RED_FLOATS) * sizeof(float), s, a);

@@ -73,39 +73,27 @@ struct DistEvalArgs {
   float* score_out;
 };
 
-// K Langevin moves (MALA or ULA) of B chains at fixed tempering weights, state in LDS: additions/mcmc.py:77-135 (mala_step), :189-221
-// (ula_step) with the step-size heuristic of :55-74, on the geometric path log pi_t = (1 - t) log p_prior + t log pi~ (ebm_mle.py's
-// tempered densities; prior.ds.kind == NONE: the target alone, e.g. the MALA chains of experiments/benchmark_utils.py:268-333)
+// K local moves of B chains in one launch, state in LDS, with the step-size heuristic of additions/mcmc.py:55-74.
+// SD_MOVE_LANGEVIN: MALA or ULA at fixed tempering weights, additions/mcmc.py:77-135 (mala_step), :189-221 (ula_step), on the geometric path
+// log pi_t = (1 - t) log p_prior + t log pi~ (ebm_mle.py's tempered densities; prior.ds.kind == NONE: the target alone, e.g. the MALA chains
+// of experiments/benchmark_utils.py:268-333).  SD_MOVE_RWMH: random-walk Metropolis on the target alone, additions/mcmc.py:256-293
+// (rwmh_step), as mcmc_sample(mcmc_type='rwmh') applies it (experiments/benchmark_utils.py:299-327); prior.ds.kind = NONE, grad = t =
+// nullptr, ula = 0.
+enum { SD_MOVE_LANGEVIN = 0, SD_MOVE_RWMH = 1 };
 struct MovesArgs {
   DistEvalArgs prior, target;   // .ds / .d / .dpad of the two ends of the path
   int B, d, K, keep_from, ula;  // chains, dimension, moves, first stored move, 1 = unadjusted
   float target_acc;             // <= 0: step sizes stay fixed
   const float* t;               // [B] tempering weight of each chain, or nullptr (1)
   float *x, *lp, *grad, *step;  // [B,d], [B], [B,d], [B]: chain state, carried in and out
-  const float *z, *u;           // injected normals [K,B,d] and uniforms [K,B] (MALA), or nullptr: counter-based Philox draws
+  const float *z, *u;           // injected normals [K,B,d] and uniforms [K,B] (not ULA), or nullptr: counter-based Philox draws
   unsigned seed_lo, seed_hi;
   long long chain0;             // global index of chain 0 (Philox counter)
   float* samples;               // [K - keep_from, B, d] states after each stored move, or nullptr
   float* acc_sum;               // [B] sum over the stored moves of min(1, acceptance ratio), or nullptr
   float* acc_last;              // [B] min(1, acceptance ratio) of the last move, or nullptr
 };
-int sd_launch_moves(const MovesArgs& a, hipStream_t s);
-
-// K random-walk Metropolis moves of B chains on the target alone, state in LDS: additions/mcmc.py:256-293 (rwmh_step) with the step-size
-// heuristic of :54-72, as mcmc_sample(mcmc_type='rwmh') applies them (experiments/benchmark_utils.py:299-327)
-struct RwmhArgs {
-  DistEvalArgs target;          // .ds / .d / .dpad
-  int B, d, K, keep_from;       // chains, dimension, moves, first stored move
-  float target_acc;             // <= 0: step sizes stay fixed
-  float *x, *lp, *step;         // [B,d], [B], [B]: chain state, carried in and out
-  const float *z, *u;           // injected normals [K,B,d] and uniforms [K,B], or nullptr: counter-based Philox draws (streams 6 / 7)
-  unsigned seed_lo, seed_hi;
-  long long chain0;             // global index of chain 0 (Philox counter)
-  float* samples;               // [K - keep_from, B, d] states after each stored move, or nullptr
-  float* acc_sum;               // [B] sum over the stored moves of min(1, acceptance ratio), or nullptr
-  float* acc_last;              // [B] min(1, acceptance ratio) of the last move, or nullptr
-};
-int sd_launch_rwmh(const RwmhArgs& a, hipStream_t s);
+int sd_launch_moves(const MovesArgs& a, int move, hipStream_t s);
 
 struct TerminalArgs {
   DistDev ref, target;

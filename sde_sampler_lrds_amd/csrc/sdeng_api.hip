@@ -1019,72 +1019,67 @@ extern "C" int sdeng_dist_eval(const sdeng_dist* dist, int32_t B, int32_t d, con
   return dist_eval(dd, B, d, dpad, x, logp_out, score_out, s);
 }
 
-// ---- Langevin moves of the annealed samplers ------------------------------------------------------------------------
-extern "C" size_t sdeng_langevin_moves_workspace_bytes(const sdeng_dist* prior, const sdeng_dist* target, int32_t d) {
+// ---- local moves in one launch: Langevin moves of the annealed samplers and random-walk Metropolis moves of the
+// learned-reference data set (experiments/benchmark_utils.py:281-290).  One host path; RWMH has no prior, gradient, weights or ULA flag.
+static size_t moves_workspace_bytes(const sdeng_dist* prior, const sdeng_dist* target, int32_t d) {
   if (!target || d < 1) return 0;
   const int dpad = pad16(d);
   return (dist_floats(*target, dpad) + (prior ? dist_floats(*prior, dpad) : 0) + 64) * sizeof(float);
 }
-extern "C" int sdeng_langevin_moves(const sdeng_dist* prior, const sdeng_dist* target, int32_t B, int32_t d, int32_t n_moves, int32_t keep_from,
-                                    int32_t unadjusted, float target_acceptance, const float* t, float* x, float* lp, float* grad, float* step,
-                                    const float* z, const float* u, uint64_t seed, int64_t chain0, float* samples, float* acc_sum,
-                                    float* acc_last, void* workspace, size_t workspace_bytes, void* stream) {
+static int run_moves(int move, const char* who, const sdeng_dist* prior, const sdeng_dist* target, int32_t B, int32_t d, int32_t n_moves,
+                     int32_t keep_from, int32_t unadjusted, float target_acceptance, const float* t, float* x, float* lp, float* grad,
+                     float* step, const float* z, const float* u, uint64_t seed, int64_t chain0, float* samples, float* acc_sum,
+                     float* acc_last, void* workspace, size_t workspace_bytes, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!target || !x || !lp || !grad || !step || B < 0 || d < 1 || n_moves < 0 || keep_from < 0) return fail(SDENG_E_INVALID, "bad argument");
-  if (d > 255) return fail(SDENG_E_UNSUPPORTED, "langevin_moves: d <= 255 (chain rows live in LDS), got %d", d);
-  if ((z == nullptr) != (u == nullptr) && !unadjusted) return fail(SDENG_E_INVALID, "MALA: inject both the normals and the uniforms, or neither");
-  if (target->kind == SDENG_DIST_CHECKERBOARD || (prior && prior->kind == SDENG_DIST_CHECKERBOARD))
-    return fail(SDENG_E_UNSUPPORTED, "langevin_moves: no moves on a checkerboard (its log-density is -inf on a set of positive mass)");
+  const bool langevin = move == SD_MOVE_LANGEVIN;
+  if (!target || !x || !lp || (langevin && !grad) || !step || B < 0 || d < 1 || n_moves < 0 || keep_from < 0 || keep_from > n_moves)
+    return fail(SDENG_E_INVALID, "%s: bad argument", who);
+  if (target->kind == SDENG_DIST_NONE) return fail(SDENG_E_INVALID, "%s: no target distribution", who);
+  if (d > 255) return fail(SDENG_E_UNSUPPORTED, "%s: d <= 255 (chain rows live in LDS), got %d", who, d);
+  if ((z == nullptr) != (u == nullptr) && !unadjusted)  // (unadjusted moves read no uniforms)
+    return fail(SDENG_E_INVALID, "%s: inject both the normals and the uniforms, or neither (unadjusted moves: the normals alone)", who);
+  if (langevin && (target->kind == SDENG_DIST_CHECKERBOARD || (prior && prior->kind == SDENG_DIST_CHECKERBOARD)))
+    return fail(SDENG_E_UNSUPPORTED, "%s: no moves on a checkerboard (its log-density is -inf on a set of positive mass)", who);
+  const bool has_prior = prior && prior->kind != SDENG_DIST_NONE;
+  SD_TRY(check_dist(*target, d));
+  if (has_prior) SD_TRY(check_dist(*prior, d));
   if (B == 0 || n_moves == 0) return 0;
   const int dpad = pad16(d);
-  const size_t need = sdeng_langevin_moves_workspace_bytes(prior, target, d);
-  if (!workspace || workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", workspace_bytes, need);
+  const size_t need = moves_workspace_bytes(prior, target, d);
+  if (!workspace || workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "%s: workspace %zu bytes, need %zu", who, workspace_bytes, need);
   float* ws = static_cast<float*>(workspace);
   MovesArgs a;
   memset(&a, 0, sizeof(a));
   SD_TRY(build_dist(*target, d, dpad, ws, a.target.ds, s));
   a.target.d = d; a.target.dpad = dpad; a.target.B = B;
   a.prior.ds.kind = SDENG_DIST_NONE;
-  if (prior && prior->kind != SDENG_DIST_NONE) SD_TRY(build_dist(*prior, d, dpad, ws + dist_floats(*target, dpad), a.prior.ds, s));
+  if (has_prior) SD_TRY(build_dist(*prior, d, dpad, ws + dist_floats(*target, dpad), a.prior.ds, s));
   a.prior.d = d; a.prior.dpad = dpad; a.prior.B = B;
   a.B = B; a.d = d; a.K = n_moves; a.keep_from = keep_from; a.ula = unadjusted ? 1 : 0; a.target_acc = target_acceptance;
   a.t = t; a.x = x; a.lp = lp; a.grad = grad; a.step = step; a.z = z; a.u = u;
   const Seed sd = split_seed(seed);
   a.seed_lo = sd.lo; a.seed_hi = sd.hi; a.chain0 = chain0;
   a.samples = samples; a.acc_sum = acc_sum; a.acc_last = acc_last;
-  SD_HIP(sd_launch_moves(a, s));
+  SD_HIP(sd_launch_moves(a, move, s));
   return 0;
 }
 
-// ---- random-walk Metropolis moves of the learned-reference data set (experiments/benchmark_utils.py:281-290) ------------------------
-extern "C" size_t sdeng_rwmh_moves_workspace_bytes(const sdeng_dist* target, int32_t d) {
-  if (!target || d < 1) return 0;
-  return (dist_floats(*target, pad16(d)) + 64) * sizeof(float);
+extern "C" size_t sdeng_langevin_moves_workspace_bytes(const sdeng_dist* prior, const sdeng_dist* target, int32_t d) {
+  return moves_workspace_bytes(prior, target, d);
 }
+extern "C" int sdeng_langevin_moves(const sdeng_dist* prior, const sdeng_dist* target, int32_t B, int32_t d, int32_t n_moves, int32_t keep_from,
+                                    int32_t unadjusted, float target_acceptance, const float* t, float* x, float* lp, float* grad, float* step,
+                                    const float* z, const float* u, uint64_t seed, int64_t chain0, float* samples, float* acc_sum,
+                                    float* acc_last, void* workspace, size_t workspace_bytes, void* stream) {
+  return run_moves(SD_MOVE_LANGEVIN, "langevin_moves", prior, target, B, d, n_moves, keep_from, unadjusted, target_acceptance, t, x, lp, grad, step,
+                   z, u, seed, chain0, samples, acc_sum, acc_last, workspace, workspace_bytes, stream);
+}
+extern "C" size_t sdeng_rwmh_moves_workspace_bytes(const sdeng_dist* target, int32_t d) { return moves_workspace_bytes(nullptr, target, d); }
 extern "C" int sdeng_rwmh_moves(const sdeng_dist* target, int32_t B, int32_t d, int32_t n_moves, int32_t keep_from, float target_acceptance,
                                 float* x, float* lp, float* step, const float* z, const float* u, uint64_t seed, int64_t chain0,
                                 float* samples, float* acc_sum, float* acc_last, void* workspace, size_t workspace_bytes, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!target || !x || !lp || !step || B < 0 || d < 1 || n_moves < 0 || keep_from < 0 || keep_from > n_moves) return fail(SDENG_E_INVALID, "bad argument");
-  if (d > 255) return fail(SDENG_E_UNSUPPORTED, "rwmh_moves: d <= 255 (chain rows live in LDS), got %d", d);
-  if ((z == nullptr) != (u == nullptr)) return fail(SDENG_E_INVALID, "rwmh_moves: inject both the normals and the uniforms, or neither");
-  if (target->kind == SDENG_DIST_NONE) return fail(SDENG_E_INVALID, "rwmh_moves: no target distribution");
-  SD_TRY(check_dist(*target, d));
-  if (B == 0 || n_moves == 0) return 0;
-  const int dpad = pad16(d);
-  const size_t need = sdeng_rwmh_moves_workspace_bytes(target, d);
-  if (!workspace || workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", workspace_bytes, need);
-  RwmhArgs a;
-  memset(&a, 0, sizeof(a));
-  SD_TRY(build_dist(*target, d, dpad, static_cast<float*>(workspace), a.target.ds, s));
-  a.target.d = d; a.target.dpad = dpad; a.target.B = B;
-  a.B = B; a.d = d; a.K = n_moves; a.keep_from = keep_from; a.target_acc = target_acceptance;
-  a.x = x; a.lp = lp; a.step = step; a.z = z; a.u = u;
-  const Seed sd = split_seed(seed);
-  a.seed_lo = sd.lo; a.seed_hi = sd.hi; a.chain0 = chain0;
-  a.samples = samples; a.acc_sum = acc_sum; a.acc_last = acc_last;
-  SD_HIP(sd_launch_rwmh(a, s));
-  return 0;
+  return run_moves(SD_MOVE_RWMH, "rwmh_moves", nullptr, target, B, d, n_moves, keep_from, 0, target_acceptance, nullptr, x, lp, nullptr, step, z, u,
+                   seed, chain0, samples, acc_sum, acc_last, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t sdeng_dist_workspace_bytes(const sdeng_dist* dist, int32_t d) {

@@ -759,23 +759,36 @@ def mmd_median(X: torch.Tensor, Y: torch.Tensor):
     return out[0], out[1]
 
 
-def langevin_moves(target, prior, x, lp, grad, step, n_moves, *, t=None, keep_from=0, unadjusted=False, target_acceptance=0.0, noise="torch",
-                   seed=0, chain0=0, want_samples=True):
-    """sdeng_langevin_moves: ``n_moves`` MALA / ULA moves of all chains in one launch (include/sdeng.h).  ``x`` [B,d], ``lp`` [B], ``grad``
-    [B,d], ``step`` [B] are updated IN PLACE.  ``noise='torch'``: the normals (and uniforms) are drawn from torch's generator move by move in
-    the order additions/mcmc.py consumes them (randn((B,d)) then rand_like(lp)), so a chain is the one the reference's loop produces;
-    ``noise='philox'``: drawn in the kernel.  Returns (samples [n_moves - keep_from, B, d] or None, acc_sum [B] or None, acc_last [B] or None)."""
+def _chain_moves(who, target, prior, x, lp, grad, step, n_moves, t, keep_from, unadjusted, target_acceptance, noise, seed, chain0, want_samples):
+    """The launcher behind langevin_moves and rwmh_moves (``who``; random-walk Metropolis has no prior / grad / t / unadjusted).  Everything
+    the kernel indexes is checked here, before anything is built or launched."""
+    langevin = who == "langevin_moves"
     require_gpu(x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x must be [B, d], got {tuple(x.shape)}")
+    B, d = x.shape
+    n_moves, keep_from = int(n_moves), int(keep_from)
+    if lp.numel() != B or step.numel() != B:
+        raise ValueError(f"{who}: lp and step must hold one value per chain (B = {B}), got {lp.numel()} and {step.numel()}")
+    if langevin and grad.shape != x.shape:
+        raise ValueError(f"{who}: grad must have the shape of x {tuple(x.shape)}, got {tuple(grad.shape)}")
+    if t is not None and t.numel() not in (1, B):
+        raise ValueError(f"{who}: t must hold one tempering weight, or one per chain (B = {B}), got {t.numel()}")
+    if not 0 <= keep_from <= n_moves:
+        raise ValueError(f"{who}: 0 <= keep_from <= n_moves, got keep_from = {keep_from}, n_moves = {n_moves}")
+    if noise not in ("torch", "philox"):
+        raise ValueError("noise: 'torch' or 'philox'")
+    state = (("x", x), ("lp", lp), ("step", step)) + ((("grad", grad),) if langevin else ())
+    for ok in (lambda v: v.dtype == torch.float32 and v.is_contiguous(), lambda v: v.is_cuda):
+        for name, v in state:
+            if not ok(v):
+                raise ValueError(f"{who}: {name} must be a contiguous float32 CUDA tensor (it is updated in place)")
+    if langevin and "Checkerboard" in (_name(target), _name(prior)):
+        raise UnsupportedByEngine(f"{who}: no moves on a checkerboard (log-density -inf on a set of positive mass; zero score)")
     lib = L.lib()
     device, keep = x.device, []
-    B, d = x.shape
-    for name, v in (("x", x), ("lp", lp), ("grad", grad), ("step", step)):
-        if v.dtype != torch.float32 or not v.is_contiguous() or not v.is_cuda:
-            raise ValueError(f"langevin_moves: {name} must be a contiguous float32 CUDA tensor (it is updated in place)")
-    if _name(target) == "Checkerboard" or _name(prior) == "Checkerboard":
-        raise UnsupportedByEngine("langevin_moves: no moves on a checkerboard (log-density -inf on a set of positive mass; zero score)")
-    dt = dist_desc(target, device, keep)
-    dp = dist_desc(prior, device, keep) if prior is not None else None
+    dt = C.byref(dist_desc(target, device, keep))
+    dp = C.byref(dist_desc(prior, device, keep)) if prior is not None else None
     z = u = None
     if noise == "torch":
         z = torch.empty(n_moves, B, d, dtype=torch.float32, device=device)
@@ -784,19 +797,30 @@ def langevin_moves(target, prior, x, lp, grad, step, n_moves, *, t=None, keep_fr
             z[m] = torch.randn((B, d), device=device)
             if u is not None:
                 u[m] = torch.rand((B,), device=device)
-    elif noise != "philox":
-        raise ValueError("noise: 'torch' or 'philox'")
     tt = None if t is None else t.detach().to(device=device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
     samples = torch.empty(n_moves - keep_from, B, d, dtype=torch.float32, device=device) if want_samples else None
-    acc = torch.empty(B, dtype=torch.float32, device=device) if not unadjusted else None
-    last = torch.empty(B, dtype=torch.float32, device=device) if not unadjusted else None
-    need = lib.sdeng_langevin_moves_workspace_bytes(C.byref(dp) if dp is not None else None, C.byref(dt), d)
+    acc = torch.zeros(B, dtype=torch.float32, device=device) if not unadjusted else None
+    last = torch.ones(B, dtype=torch.float32, device=device) if not unadjusted else None
+    need = lib.sdeng_rwmh_moves_workspace_bytes(dt, d) if not langevin else lib.sdeng_langevin_moves_workspace_bytes(dp, dt, d)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
     ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
-    L.check(lib.sdeng_langevin_moves(C.byref(dp) if dp is not None else None, C.byref(dt), B, d, int(n_moves), int(keep_from), int(bool(unadjusted)),
-                                     float(target_acceptance), ptr(tt), x.data_ptr(), lp.data_ptr(), grad.data_ptr(), step.data_ptr(), ptr(z), ptr(u),
-                                     int(seed), int(chain0), ptr(samples), ptr(acc), ptr(last), ws.data_ptr(), ws.numel(), _stream_ptr(device)))
+    tail = (ptr(z), ptr(u), int(seed), int(chain0), ptr(samples), ptr(acc), ptr(last), ws.data_ptr(), ws.numel(), _stream_ptr(device))
+    if not langevin:
+        L.check(lib.sdeng_rwmh_moves(dt, B, d, n_moves, keep_from, float(target_acceptance), ptr(x), ptr(lp), ptr(step), *tail))
+    else:
+        L.check(lib.sdeng_langevin_moves(dp, dt, B, d, n_moves, keep_from, int(bool(unadjusted)), float(target_acceptance), ptr(tt), ptr(x), ptr(lp),
+                                         ptr(grad), ptr(step), *tail))
     return samples, acc, last
+
+
+def langevin_moves(target, prior, x, lp, grad, step, n_moves, *, t=None, keep_from=0, unadjusted=False, target_acceptance=0.0, noise="torch",
+                   seed=0, chain0=0, want_samples=True):
+    """sdeng_langevin_moves: ``n_moves`` MALA / ULA moves of all chains in one launch (include/sdeng.h).  ``x`` [B,d], ``lp`` [B], ``grad``
+    [B,d], ``step`` [B] are updated IN PLACE.  ``noise='torch'``: the normals (and uniforms) are drawn from torch's generator move by move in
+    the order additions/mcmc.py consumes them (randn((B,d)) then rand_like(lp)), so a chain is the one the reference's loop produces;
+    ``noise='philox'``: drawn in the kernel.  Returns (samples [n_moves - keep_from, B, d] or None, acc_sum [B] or None, acc_last [B] or None)."""
+    return _chain_moves("langevin_moves", target, prior, x, lp, grad, step, n_moves, t, keep_from, unadjusted, target_acceptance, noise, seed,
+                        chain0, want_samples)
 
 
 def rwmh_moves(target, x, lp, step, n_moves, *, keep_from=0, target_acceptance=0.0, noise="torch", seed=0, chain0=0, want_samples=True):
@@ -804,40 +828,8 @@ def rwmh_moves(target, x, lp, step, n_moves, *, keep_from=0, target_acceptance=0
     ``step`` [B] are updated IN PLACE.  ``noise='torch'``: per move ``torch.randn((B, d))`` then ``torch.rand((B,))`` on the device, the order
     additions/mcmc.py:rwmh_step consumes them; ``noise='philox'``: drawn in the kernel (streams 6 / 7).  Everything the kernel indexes is
     checked here.  Returns (samples [n_moves - keep_from, B, d] or None, acc_sum [B], acc_last [B])."""
-    require_gpu(x)
-    if x.dim() != 2:
-        raise ValueError(f"rwmh_moves: x must be [B, d], got {tuple(x.shape)}")
-    B, d = x.shape
-    n_moves, keep_from = int(n_moves), int(keep_from)
-    if lp.numel() != B or step.numel() != B:
-        raise ValueError(f"rwmh_moves: lp and step must hold one value per chain (B = {B}), got {lp.numel()} and {step.numel()}")
-    if not 0 <= keep_from <= n_moves:
-        raise ValueError(f"rwmh_moves: 0 <= keep_from <= n_moves, got keep_from = {keep_from}, n_moves = {n_moves}")
-    if noise not in ("torch", "philox"):
-        raise ValueError("noise: 'torch' or 'philox'")
-    for ok in (lambda v: v.dtype == torch.float32 and v.is_contiguous(), lambda v: v.is_cuda):
-        for name, v in (("x", x), ("lp", lp), ("step", step)):
-            if not ok(v):
-                raise ValueError(f"rwmh_moves: {name} must be a contiguous float32 CUDA tensor (it is updated in place)")
-    lib = L.lib()
-    device, keep = x.device, []
-    dt = dist_desc(target, device, keep)
-    z = u = None
-    if noise == "torch":
-        z = torch.empty(n_moves, B, d, dtype=torch.float32, device=device)
-        u = torch.empty(n_moves, B, dtype=torch.float32, device=device)
-        for m in range(n_moves):  # the reference's consumption order: one randn per proposal, then one rand per accept test
-            z[m] = torch.randn((B, d), device=device)
-            u[m] = torch.rand((B,), device=device)
-    samples = torch.empty(n_moves - keep_from, B, d, dtype=torch.float32, device=device) if want_samples else None
-    acc = torch.zeros(B, dtype=torch.float32, device=device)
-    last = torch.ones(B, dtype=torch.float32, device=device)
-    ws = torch.empty(max(lib.sdeng_rwmh_moves_workspace_bytes(C.byref(dt), d), 16), dtype=torch.uint8, device=device)
-    ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
-    L.check(lib.sdeng_rwmh_moves(C.byref(dt), B, d, n_moves, keep_from, float(target_acceptance), x.data_ptr(), lp.data_ptr(), step.data_ptr(),
-                                 ptr(z), ptr(u), int(seed), int(chain0), ptr(samples), acc.data_ptr(), last.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 _stream_ptr(device)))
-    return samples, acc, last
+    return _chain_moves("rwmh_moves", target, None, x, lp, None, step, n_moves, None, keep_from, False, target_acceptance, noise, seed, chain0,
+                        want_samples)
 
 
 def _net_only_desc(ctrl, t_unique: torch.Tensor, n_times: int, d: int, device, keep: list, who="ctrl_vjp", own_workspace=False):

@@ -8,28 +8,9 @@ import torch
 
 from tests import golden_cases as gc
 from tests import rwmh_cases as rc
+from tests.cpu_generator import CpuGenerator
 
 FLIP = 1e-3  # a chain whose accept / reject decision fell within round-off of its threshold differs by a whole proposal: max|dx| > 1e-3
-
-
-class _CpuGenerator:
-    """Draw every random number from torch's CPU generator (the one the fixtures were generated with) and move it to the chains' device."""
-
-    def __enter__(self):
-        self.saved = {n: getattr(torch, n) for n in ("randn", "rand", "randn_like")}
-        s = self.saved
-
-        def shaped(fn):
-            def wrap(*size, device=None, dtype=None, generator=None, **kw):
-                return fn(*size, dtype=dtype, **kw).to(device or "cpu")
-            return wrap
-        torch.randn, torch.rand = shaped(s["randn"]), shaped(s["rand"])
-        torch.randn_like = lambda t, **kw: s["randn"](t.shape, dtype=t.dtype).to(t.device)
-        return self
-
-    def __exit__(self, *exc):
-        for n, f in self.saved.items():
-            setattr(torch, n, f)
 
 
 def _host_arm(target, x0, lp0, step0, n_moves, target_acceptance):
@@ -241,7 +222,7 @@ def test_rwmh_fixtures_through_the_native_route(gpu, name):
     calls = ebm_mle._native_calls[0]
     x_init = rc.rwmh_x_init(m, target)  # (outside the patch: it draws from a generator of its own)
     torch.manual_seed(m["seed"])
-    with _CpuGenerator():
+    with CpuGenerator():
         out = mcmc_sample(gpu, target, x_init, **rc.rwmh_kwargs(m))
     assert ebm_mle._native_calls[0] == calls + 1 and out.shape == c["samples"].shape
     err = (_per_chain(out, n_chains) - _per_chain(c["samples"], n_chains)).abs().amax(dim=(0, 2))

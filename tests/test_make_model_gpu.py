@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from sde_sampler_lrds_amd.experiments.benchmark_utils import make_model, make_target_details
+from tests.cpu_generator import CpuGenerator
 
 
 def _train(n):
@@ -255,29 +256,6 @@ def test_logreg_design_matrix_through_l2_matches_oracle(gpu, name):
 
 
 # ---- SURVEY 8f-4 on the HIP path: the reference's own sampler output, with the HIP kernels as the density ----------------------
-class _CpuGenerator:
-    """Draw every random number of the samplers from torch's CPU generator (the one the fixtures were generated with) and move it to
-    the chains' device: same seed, same consumption order -> the reference's random numbers, on GPU tensors."""
-
-    def __enter__(self):
-        self.saved = {n: getattr(torch, n) for n in ("randn", "rand", "randn_like", "rand_like", "multinomial")}
-        s = self.saved
-
-        def shaped(fn):
-            def wrap(*size, device=None, dtype=None, generator=None, **kw):
-                return fn(*size, dtype=dtype, **kw).to(device or "cpu")
-            return wrap
-        torch.randn, torch.rand = shaped(s["randn"]), shaped(s["rand"])
-        torch.randn_like = lambda t, **kw: s["randn"](t.shape, dtype=t.dtype).to(t.device)
-        torch.rand_like = lambda t, **kw: s["rand"](t.shape, dtype=t.dtype).to(t.device)
-        torch.multinomial = lambda w, n, replacement=False, **kw: s["multinomial"](w.cpu(), n, replacement=replacement).to(w.device)
-        return self
-
-    def __exit__(self, *exc):
-        for n, f in self.saved.items():
-            setattr(torch, n, f)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", __import__("tests.golden_cases", fromlist=["x"]).SAMPLER_CASES)
 def test_annealed_samplers_on_hip_densities_match_reference_fixture(gpu, name):
@@ -310,7 +288,7 @@ def test_annealed_samplers_on_hip_densities_match_reference_fixture(gpu, name):
         from sde_sampler_lrds_amd.eq.sdes import VP
         kw.update(use_pdds_weights=True, sde=VP(0.1, 10.0, 1.0, terminal_t=1.0).to(gpu))
     torch.manual_seed(m["seed"])
-    with _CpuGenerator():
+    with CpuGenerator():
         if m["sampler"] == "smc":
             samples, steps_out, diags = ebm_mle.smc_sampler(x_init.to(gpu), times.to(gpu), fn, m["n_warm"], m["n_steps"], steps.clone().to(gpu), **kw)
         else:

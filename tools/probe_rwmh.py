@@ -7,7 +7,7 @@ torch's generator (two small generator launches per move remain), one launch wit
 and at B = 4096, d = 24 on a 3-component mixture.
 
     python tools/probe_rwmh.py [--reps 5]
-    rocprofv3 --kernel-trace --stats ... -- python tools/probe_rwmh.py --kernel-only      (kernel time alone: k_rwmh_moves in the stats)
+    rocprofv3 --kernel-trace --stats ... -- python tools/probe_rwmh.py --kernel-only      (kernel time alone: k_chain_moves<1> in the stats)
 """
 import argparse
 import os
