@@ -20,14 +20,12 @@ import weakref
 import torch
 
 from . import _lib as L
+from . import routes as R
+from .routes import UnsupportedByEngine, diagonal_reference, resolve_reference  # noqa: F401  (their names here)
+from .routes import name_of as _name, self_of as _self_of
 
-
-class UnsupportedByEngine(NotImplementedError):
-    pass
-
-
-def _name(obj):
-    return type(obj).__name__
+adjoint_ctrl_ok, cmcd_adjoint_ok = R.kl_native, R.cmcd_native  # the gates of the two one-launch adjoints, under the names they have here
+_DIST_REFUSALS = {"PhiFour": "PhiFour: only the 1-D Dirichlet-0 untilted lattice", "Rings": "Rings: at most 8 radii"}  # where dist_kind has no kind
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -41,23 +39,18 @@ def _dev_f32(t: torch.Tensor, device, keep: list):
     return t.data_ptr()
 
 
-def _self_of(fn):
-    return getattr(fn, "__self__", None)
-
-
 # ------------------------------------------------------------------------------------------------
 # distributions
 # ------------------------------------------------------------------------------------------------
 def dist_desc(obj, device, keep, clip=None, score_only=False) -> L.Dist:
-    """Distribution object -> sdeng_dist (distr/*.py parameters).  ``score_only``: the descriptor is the target of a Score / Lerp /
-    CancelDrift control and only its score is evaluated -- the one use a full-covariance mixture has a kernel for."""
+    """Distribution object -> sdeng_dist (distr/*.py parameters) of the kind ``routes.dist_kind`` names: classifier and builder cannot disagree."""
     ds = L.Dist()
     ds.clip = float(clip) if clip else 0.0
-    if obj is None:
-        ds.kind = L.DIST_NONE
-        return ds
-    n = _name(obj)
-    if n == "IsotropicGauss":
+    kind = R.dist_kind(obj, score_only)
+    if kind is None:
+        raise UnsupportedByEngine(_DIST_REFUSALS.get(_name(obj), f"no HIP log-density/score for distribution {_name(obj)}"))
+    ds.kind = kind
+    if kind == L.DIST_ISO_GAUSS:
         # the four scalars are read back from the device once per parameter version (a read-back synchronises the stream)
         key = (obj.loc._version, obj.scale._version, obj.loc.data_ptr(), obj.scale.data_ptr())
         hit = getattr(obj, "_sdeng_scalars", None)
@@ -66,69 +59,46 @@ def dist_desc(obj, device, keep, clip=None, score_only=False) -> L.Dist:
             var = scale ** 2
             hit = (key, (float(loc), float(scale), float(-0.5 * obj.dim * (2.0 * math.pi * var).log()), float(var)))  # distr/gauss.py:759
             obj._sdeng_scalars = hit
-        ds.kind = L.DIST_ISO_GAUSS
         ds.p0, ds.p1, ds.p2, ds.p3 = hit[1]
-        return ds
-    if n in ("GMM", "TwoModes", "ManyModes", "BracketTwoModes", "Gauss", "Delta"):
-        if getattr(obj, "mixture_weights", None) is None:
-            ds.kind = L.DIST_GAUSS_DIAG
-            ds.k = 1
-            ds.loc = _dev_f32(obj.loc.reshape(-1), device, keep)
-            ds.scale = _dev_f32(obj.scale.reshape(-1), device, keep)
-        else:
-            ds.kind = L.DIST_GMM_DIAG
-            ds.k = int(obj.loc.shape[0])
-            ds.loc = _dev_f32(obj.loc, device, keep)
-            ds.scale = _dev_f32(obj.scale, device, keep)
+    elif kind in (L.DIST_GAUSS_DIAG, L.DIST_GMM_DIAG):  # loc / scale [K,d]; a Gaussian is the one-component case without weights
+        ds.k = int(obj.loc.shape[0])
+        ds.loc = _dev_f32(obj.loc, device, keep)
+        ds.scale = _dev_f32(obj.scale, device, keep)
+        if kind == L.DIST_GMM_DIAG:
             ds.w = _dev_f32(obj.mixture_weights, device, keep)
-        return ds
-    if n == "PhiFour":
-        if getattr(obj, "dim_phys", 1) != 1 or tuple(getattr(obj, "bc", ("dirichlet", 0))) != ("dirichlet", 0) or getattr(obj, "tilt", None):
-            raise UnsupportedByEngine("PhiFour: only the 1-D Dirichlet-0 untilted lattice")
-        ds.kind = L.DIST_PHI4
+    elif kind == L.DIST_PHI4:
         ds.p0, ds.p1, ds.p2 = scalar_of(obj.a), scalar_of(obj.b), scalar_of(obj.beta)
-        return ds
-    if n == "GaussFull":
+    elif kind == L.DIST_GAUSS_FULL:
         key = (obj.cov._version, obj.cov.data_ptr(), str(device))
         hit = getattr(obj, "_sdeng_chol", None)
         if hit is None or hit[0] != key:  # Cholesky factor, its inverse and log-determinant once per parameter version
             tril = torch.linalg.cholesky(obj.cov.detach().float().cpu())
             hit = (key, torch.linalg.inv(tril).to(device), float(tril.diagonal().log().sum()), tril.to(device))
             obj._sdeng_chol = hit
-        ds.kind = L.DIST_GAUSS_FULL
         ds.loc = _dev_f32(obj.loc, device, keep)
         ds.scale = _dev_f32(obj.prec, device, keep)
         ds.w = _dev_f32(hit[1], device, keep)
         ds.p0 = hit[2]
         ds.aux = _dev_f32(hit[3], device, keep)  # L itself: GaussFull.sample (x0_dist)
-        return ds
-    if n in ("LogisticRegression", "SyntheticLogReg"):
-        ds.kind = L.DIST_LOGREG
+    elif kind == L.DIST_LOGREG:
         ds.k = int(obj.X_train.shape[0])
         ds.loc = _dev_f32(obj.X_train, device, keep)
         ds.scale = _dev_f32(obj.y_train, device, keep)
         ds.p0, ds.p1, ds.p2 = scalar_of(obj.weight_scale), scalar_of(obj.intercept_mean), scalar_of(obj.intercept_scale)
         ds.p3 = scalar_of(obj.threshold)
-        return ds
-    if n == "Rings":  # distr/rings.py:38-109
-        ds.kind = L.DIST_RINGS
+    elif kind == L.DIST_RINGS:  # distr/rings.py:38-109
         ds.k = int(obj.radiuses.shape[0])
-        if ds.k > 8:
-            raise UnsupportedByEngine("Rings: at most 8 radii")
         ds.loc = _dev_f32(obj.radiuses, device, keep)
         ds.w = _dev_f32(obj.radius_dist.mixture_distribution.probs, device, keep)
         ds.p0 = float(obj.radius_dist.component_distribution.scale.reshape(-1)[0])
-        return ds
-    if n == "Checkerboard":  # distr/checkerboard.py: uniform squares; this package's mirror and the reference's object alike
+    elif kind == L.DIST_CHECKERBOARD:  # distr/checkerboard.py: uniform squares; this package's mirror and the reference's object alike
         comp = obj.distr.component_distribution.base_dist
-        ds.kind = L.DIST_CHECKERBOARD
         ds.k = int(comp.low.shape[0])
         ds.loc = _dev_f32(comp.low, device, keep)
         ds.scale = _dev_f32(comp.high, device, keep)
         with torch.no_grad():  # each square's log-density: the object's own expression at the square's centre (it is constant inside)
             ds.w = _dev_f32(obj.unnorm_log_prob((comp.low + comp.high) / 2.0).reshape(-1), device, keep)
-        return ds
-    if n in ("GMMFull", "TwoModesFull") and score_only:
+    elif kind == L.DIST_GMM_FULL:
         # score_mog_full inside the step loop (distr/gauss.py:110-121): the kernel takes each covariance in its eigen form, decomposed
         # once per parameter version in fp64 (the reference inverts the covariances once, in fp32, at construction)
         cov = getattr(obj, "cov", None)
@@ -138,14 +108,12 @@ def dist_desc(obj, device, keep, clip=None, score_only=False) -> L.Dist:
         else:
             eig = _EIGH.get(obj.prec, lambda v: torch.linalg.eigh(v.detach().double()))
             evals, evecs = (1.0 / eig[0]).float(), eig[1].float()
-        ds.kind = L.DIST_GMM_FULL
         ds.k = int(obj.loc.shape[0])
         ds.loc = _dev_f32(obj.loc, device, keep)
         ds.scale = _dev_f32(evals, device, keep)
         ds.w = _dev_f32(obj.mixture_weights, device, keep)
         ds.aux = _dev_f32(evecs, device, keep)
-        return ds
-    raise UnsupportedByEngine(f"no HIP log-density/score for distribution {n}")
+    return ds
 
 
 class InitialDraw:
@@ -225,38 +193,28 @@ def _time_embed(te, device, keep) -> L.TimeEmbed:
 
 
 def unwrap_ctrl(ctrl):
-    """(control module the kernels know, RemoveReferenceCtrl wrapper or None).  Peels the EMA wrapper (``AveragedModel``,
-    solver/oc.py:69-78) and ``RemoveReferenceCtrl`` (models/reparam.py:46-64: ``score(t, x) - ref_score(t, x)``), which the step loop
-    applies as SDENG_FLAG_REMOVE_REF -- only in the form upstream's forward can evaluate (``use_rescaling=False``)."""
-    if _name(ctrl) == "AveragedModel":
-        ctrl = ctrl.module
-    wrapper = None
-    if _name(ctrl) == "RemoveReferenceCtrl":
-        wrapper = ctrl
-        if ctrl.use_rescaling:
-            raise UnsupportedByEngine("RemoveReferenceCtrl(use_rescaling=True): upstream's forward needs the `sde` its constructor refuses "
-                                      "(models/reparam.py:52, :60) and raises AttributeError; use_rescaling=False is on the HIP path")
-        ctrl = ctrl.score
-        if _name(ctrl) == "AveragedModel":
-            ctrl = ctrl.module
-    return ctrl, wrapper
+    """(control module the kernels know, RemoveReferenceCtrl wrapper or None); the wrapper only in the form upstream's forward can evaluate."""
+    rec = R.describe_ctrl(ctrl)
+    if rec.wrapper is not None and rec.wrapper.use_rescaling:
+        raise UnsupportedByEngine("RemoveReferenceCtrl(use_rescaling=True): upstream's forward needs the `sde` its constructor refuses "
+                                  "(models/reparam.py:52, :60) and raises AttributeError; use_rescaling=False is on the HIP path")
+    return rec.ctrl, rec.wrapper
 
 
 def net_desc(ctrl, device, keep) -> L.Net:
     """ClippedCtrl / ScoreCtrl / LerpCtrl / CancelDriftCtrl around FourierMLP(4 layers, 64 channels, GELU) -> sdeng_net."""
     ctrl, _ = unwrap_ctrl(ctrl)
-    kinds = {"ClippedCtrl": L.CTRL_CLIPPED, "ScoreCtrl": L.CTRL_SCORE, "LerpCtrl": L.CTRL_LERP, "CancelDriftCtrl": L.CTRL_CANCEL_DRIFT}
-    if _name(ctrl) not in kinds:
+    rec = R.describe_ctrl(ctrl)
+    if rec.kind is None:
         raise UnsupportedByEngine(f"control wrapper {_name(ctrl)} has no HIP kernel")
     net = ctrl.base_model
-    if _name(net) != "FourierMLP" or net.channels != 64 or len(net.hidden_layer) != 2 or _name(net.input_embed) != "Linear":
-        raise UnsupportedByEngine("drift net must be FourierMLP(num_layers=4, channels=64, use_angle_encoding=False)")
-    if _name(net.activation) != "GELU" or getattr(net.activation, "approximate", "none") != "none":
-        raise UnsupportedByEngine("activation must be exact-erf GELU")
+    fault = R.net_fault(net)
+    if fault:
+        raise UnsupportedByEngine(fault)
     if getattr(ctrl, "hard_constrain", False):
         raise UnsupportedByEngine("LerpCtrl(hard_constrain=True)")
     n = L.Net()
-    n.ctrl_kind = kinds[_name(ctrl)]
+    n.ctrl_kind = rec.kind
     n.w_in, n.b_in = _dev_f32(net.input_embed.weight, device, keep), _dev_f32(net.input_embed.bias, device, keep)
     n.w_h1, n.b_h1 = _dev_f32(net.hidden_layer[0].weight, device, keep), _dev_f32(net.hidden_layer[0].bias, device, keep)
     n.w_h2, n.b_h2 = _dev_f32(net.hidden_layer[1].weight, device, keep), _dev_f32(net.hidden_layer[1].bias, device, keep)
@@ -273,40 +231,19 @@ def net_desc(ctrl, device, keep) -> L.Net:
 
 def ctrl_target(ctrl):
     """Distribution whose score ScoreCtrl/LerpCtrl mixes in (``target_score`` is a bound ``Distribution.score``)."""
-    ctrl, _ = unwrap_ctrl(ctrl)
-    if _name(ctrl) == "ClippedCtrl":
+    rec = R.describe_ctrl(unwrap_ctrl(ctrl)[0])
+    if rec.kind == L.CTRL_CLIPPED:
         return None, None
-    tgt = _self_of(ctrl.target_score)
-    if tgt is None:
+    if rec.target is None:
         raise UnsupportedByEngine("ScoreCtrl.target_score must be a bound Distribution.score")
-    prior = None
-    if _name(ctrl) == "LerpCtrl":
-        prior = _self_of(ctrl.prior_score)
-        if prior is None or _name(prior) != "IsotropicGauss":
-            raise UnsupportedByEngine("LerpCtrl.prior_score must be IsotropicGauss.score")
-    return tgt, prior
+    if rec.kind == L.CTRL_LERP and rec.lerp_prior is None:
+        raise UnsupportedByEngine("LerpCtrl.prior_score must be IsotropicGauss.score")
+    return rec.target, rec.lerp_prior
 
 
 # ------------------------------------------------------------------------------------------------
 # reference drift
 # ------------------------------------------------------------------------------------------------
-def resolve_reference(reference_ctrl):
-    """``reference_ctrl`` callable -> ('none'|'gaussian'|'gmm', params).  Recognises the bound
-    ``RDS.reference_ctrl`` (solver/oc.py:590-592 + ``reference_distr_utils``) and this package's
-    ``MarginalReference`` objects."""
-    if reference_ctrl is None:
-        return "none", {}
-    owner = _self_of(reference_ctrl) or reference_ctrl
-    utils = getattr(owner, "reference_distr_utils", None)
-    if utils is None:
-        raise UnsupportedByEngine("reference_ctrl is an opaque callable: pass RDS.reference_ctrl or a MarginalReference")
-    if "means_init" in utils:
-        return "gmm", utils  # diagonal [K,d], full [K,d,d] or the eigen form (D, P): ref_desc picks the kernel
-    if "x_init" in utils:
-        return "gaussian", utils  # diagonal [d], a covariance matrix [d,d] or its eigen form (D, P)
-    raise UnsupportedByEngine("EBM ('nn') references need autograd inside the step: not on the HIP path")
-
-
 class _TensorCache:
     """Derived facts about a caller's tensor (shared-variance test, eigendecomposition), keyed by the tensor OBJECT: the entry holds a
     weak reference, so it dies with the tensor and a new tensor the allocator places at the same address can never match; the
@@ -658,15 +595,12 @@ def euler_states(sde, timesteps: torch.Tensor, x: torch.Tensor, increments=None,
         else:
             desc.net = net_desc(ctrl, device, keep)
             tgt, lerp_prior = ctrl_target(ctrl)
-            if tgt is not None:
-                desc.target = dist_desc(tgt, device, keep)
-            if lerp_prior is not None:
-                desc.prior = dist_desc(lerp_prior, device, keep)
+            desc.target, desc.prior = dist_desc(tgt, device, keep), dist_desc(lerp_prior, device, keep)
         for k in range(N):
             s = ts[k]
             g = base.diff(s, None)
             coef[k, 0], coef[k, 1], coef[k, 2], coef[k, 3] = T - s, base.drift_coeff_t(s), g, torch.square(g)
-            if ctrl is not None and _name(ctrl) == "LerpCtrl":  # reparam.py:175, :199 at the net's time T - s
+            if R.describe_ctrl(ctrl).own_kind == L.CTRL_LERP:  # reparam.py:175, :199 at the net's time T - s
                 coef[k, 7], coef[k, 8] = base.diff(T - s, None), (T - s) / T
     dt = ts[1:] - ts[:-1]
     coef[:, 4] = dt
@@ -925,51 +859,6 @@ class VjpSession:
         return self.rows.result()
 
 
-def diagonal_reference(kind, utils) -> bool:
-    """No reference drift, or a Gaussian / mixture reference with diagonal covariances (what sdeng_kl_adjoint differentiates in closed form)."""
-    if kind == "none":
-        return True
-    if kind == "gaussian":
-        v = utils["var_init"]
-        return not isinstance(v, tuple) and v.dim() <= 1
-    if kind == "gmm":
-        v = utils["variances_init"]
-        return not isinstance(v, tuple) and v.dim() == 2
-    return False
-
-
-# targets whose ``score`` is the base class's autograd evaluation WITHOUT a graph (distr/base.py:146-154): back-propagation through the
-# trajectory sees it as a constant of x, in the reference and here
-_GRAPHLESS_SCORE = ("LogisticRegression", "SyntheticLogReg")
-
-
-def adjoint_ctrl_ok(ctrl) -> bool:
-    """Does sdeng_kl_adjoint differentiate this control?  ClippedCtrl over a FourierMLP, or a plain ScoreCtrl over one whose target is a
-    diagonal mixture or the phi^4 lattice (BASELINE configs 1 and 3: DDS on TwoModes, PIS on PhiFour) and whose score model, if any, is a TimeEmbed."""
-    name = type(ctrl).__name__
-    if type(getattr(ctrl, "base_model", None)).__name__ != "FourierMLP":
-        return False
-    if name == "ClippedCtrl":
-        return True
-    if name not in ("ScoreCtrl", "LerpCtrl", "CancelDriftCtrl"):
-        return False
-    if name == "LerpCtrl" and (getattr(ctrl, "hard_constrain", False) or _name(_self_of(ctrl.prior_score)) != "IsotropicGauss"):
-        return False
-    tgt = _self_of(ctrl.target_score)
-    if tgt is None:
-        return False
-    if _name(tgt) == "PhiFour":
-        try:
-            dist_desc(tgt, "cpu", [])  # (the 1-D Dirichlet-0 untilted lattice only)
-        except UnsupportedByEngine:
-            return False
-    elif _name(tgt) in _GRAPHLESS_SCORE:
-        pass  # the score of every row comes from the HIP score kernel and is a constant of x, as upstream's autograd-made score is
-    elif _name(tgt) not in ("GMM", "TwoModes", "ManyModes", "BracketTwoModes") or getattr(tgt, "mixture_weights", None) is None:
-        return False
-    return ctrl.score_model is None or _name(ctrl.score_model) == "TimeEmbed"
-
-
 def kl_adjoint(ctrl, coef: torch.Tensor, xs: torch.Tensor, z, w: torch.Tensor, lam_n: torch.Tensor, *, lin: bool, ito: bool, ref=("none", {})):
     """sdeng_kl_adjoint: the whole adjoint recursion of KL training in one launch (ClippedCtrl, or ScoreCtrl on a diagonal mixture target; no
     reference, or a diagonal Gaussian / mixture reference).  ``coef`` [N,16] on the device, ``xs`` [N,B,d] = x_0 .. x_{N-1}, ``z`` [N,B,d]
@@ -989,14 +878,12 @@ def kl_adjoint(ctrl, coef: torch.Tensor, xs: torch.Tensor, z, w: torch.Tensor, l
         raise UnsupportedByEngine("kl_adjoint: ClippedCtrl, or ScoreCtrl on a diagonal mixture target")
     score = desc.net.ctrl_kind != L.CTRL_CLIPPED
     ext_score = None
-    if score:
-        tgt, lerp_prior = ctrl_target(ctrl)
-        if _name(tgt) in _GRAPHLESS_SCORE:
-            _, ext_score = dist_eval(tgt, xs.reshape(N * B, d), want_logp=False, want_score=True)
-        else:
-            desc.target = dist_desc(tgt, device, keep)
-        if lerp_prior is not None:
-            desc.prior = dist_desc(lerp_prior, device, keep)
+    tgt, lerp_prior = ctrl_target(ctrl)  # (None, None) for a ClippedCtrl: SDENG_DIST_NONE descriptors
+    if R.dist_kind(tgt) in R.GRAPHLESS_TARGETS:
+        _, ext_score = dist_eval(tgt, xs.reshape(N * B, d), want_logp=False, want_score=True)
+    else:
+        desc.target = dist_desc(tgt, device, keep)
+    desc.prior = dist_desc(lerp_prior, device, keep)
     desc.ref = ref_desc(ref[0], ref[1], device, keep)
     if desc.ref.kind not in (L.REF_NONE, L.REF_GAUSS_DIAG, L.REF_GMM_DIAG):
         raise UnsupportedByEngine("kl_adjoint: diagonal references only")
@@ -1032,47 +919,6 @@ def ctrl_forward_rows(ctrl, t_unique: torch.Tensor, xs: torch.Tensor) -> torch.T
     return u.view(M, B, d)
 
 
-
-_DIAG_TARGETS = ("GMM", "TwoModes", "ManyModes", "BracketTwoModes", "Gauss")
-
-
-def cmcd_adjoint_ok(loss) -> bool:
-    """Does sdeng_cmcd_kl_adjoint differentiate this ControlledLangevinSDELoss?  Looks at types and attributes only (no descriptor, no
-    read-back): a ClippedCtrl or plain ScoreCtrl over a FourierMLP; an IsotropicGauss or diagonal Gauss prior; a diagonal mixture /
-    Gaussian, untilted 1-D Dirichlet-0 phi^4 or logistic-regression (d <= 64) target, d <= 128 -- and the ScoreCtrl's target is the SDE's.
-    Rings, checkerboard and full-covariance priors / targets keep the per-step adjoint."""
-    ctrl, sde = loss.generative_ctrl, loss.sde
-    if _name(ctrl) not in ("ClippedCtrl", "ScoreCtrl") or _name(getattr(ctrl, "base_model", None)) != "FourierMLP":
-        return False
-    if not getattr(loss, "use_rescaling", True):
-        return False
-    target, prior = _self_of(getattr(sde, "target_score", None)), _self_of(getattr(sde, "prior_score", None))
-    if target is None or prior is None:
-        return False
-    if _name(prior) == "Gauss":
-        if getattr(prior, "mixture_weights", None) is not None or getattr(prior, "scale", None) is None:
-            return False
-    elif _name(prior) != "IsotropicGauss":
-        return False
-    dim = int(getattr(target, "dim", 0) or 0)
-    if dim < 1 or dim > 128:
-        return False
-    n = _name(target)
-    if n == "PhiFour":
-        if getattr(target, "dim_phys", 1) != 1 or tuple(getattr(target, "bc", ("dirichlet", 0))) != ("dirichlet", 0) or getattr(target, "tilt", None):
-            return False
-    elif n in _GRAPHLESS_SCORE:
-        if dim > 64:
-            return False
-    elif n not in _DIAG_TARGETS:
-        return False
-    if _name(ctrl) == "ScoreCtrl":
-        if _self_of(ctrl.target_score) is not target:
-            return False
-        return ctrl.score_model is None or _name(ctrl.score_model) == "TimeEmbed"
-    return True
-
-
 def cmcd_kl_adjoint(ctrl, sde, coef: torch.Tensor, xs: torch.Tensor, cbar: torch.Tensor, w: torch.Tensor, lam_n: torch.Tensor, score_ext=None):
     """sdeng_cmcd_kl_adjoint: the adjoint of CMCD's KL training over the N + 1 evaluation points in one launch.  ``coef`` [N+1,16] the CMCD
     table of the step loop (device), ``xs`` [N+1,B,d] = x_0 .. x_N, ``cbar`` [N,B,d] = cost_j dt_j + db_j, ``w`` [B,1] = d loss / d rnd,
@@ -1101,7 +947,7 @@ def cmcd_kl_adjoint(ctrl, sde, coef: torch.Tensor, xs: torch.Tensor, cbar: torch
     desc.cmcd_g = scalar_of(sde.diff_coeff)
     desc.cmcd_clip = scalar_of(sde.clip_score) if sde.clip_score else 0.0
     rows = _RowArrays(_f32c(xs).view(M * B, d))
-    if _name(target) in _GRAPHLESS_SCORE and score_ext is None:
+    if desc.target.kind in R.GRAPHLESS_TARGETS and score_ext is None:
         _, score_ext = dist_eval(target, rows.x, want_logp=False, want_score=True)
     if score_ext is not None:
         score_ext = _f32c(score_ext)

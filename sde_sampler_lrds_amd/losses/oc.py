@@ -27,6 +27,7 @@ import torch
 
 from .. import _lib as L
 from .. import engine as E
+from .. import routes as R
 from ..utils.common import Results, make_results
 from . import training as T
 from .training import _capturable, _FusedIntegral, _GraphedAdjointStep, _graphed_step, _IntegralPass, ctrl_batched, fused_net_view, fused_training_ok, vjp_param_grads  # noqa: F401  (all stay reachable here)
@@ -185,12 +186,9 @@ class BaseOCLoss:
 
     def _integral_pass(self, t_unique, xs, zc):
         """The batched control pass, eager or -- ``graph_training`` -- as a captured graph per (shape, control): at the reference's
-        training sizes the ~150 small kernels of its forward + backward are host-launch bound (tools/probe_training.py).  Only for the
-        pure-torch controls (ClippedCtrl over a FourierMLP); anything else, or a capture that fails, runs eagerly."""
-        # RemoveReferenceCtrl: u = inner - ref_score and ref_score has no parameters, so s - s.detach() of the inner control carries the
-        # same (zero) value and the same gradient
-        ctrl = E.unwrap_ctrl(self.generative_ctrl)[0] if type(self.generative_ctrl).__name__ == "RemoveReferenceCtrl" else self.generative_ctrl
-        if self.fused_training and fused_training_ok(ctrl):
+        training sizes the ~150 small kernels of its forward + backward are host-launch bound (tools/probe_training.py).  ``routes.lv_route`` decides."""
+        route, ctrl = R.lv_route(self)
+        if route == "fused":
             # the drift net of every RDS / LRDS solver (conf/model/basic.yaml), and the ScoreCtrl of PIS / DDS / DIS (conf/model/score.yaml):
             # fused HIP forward + backward of the net (csrc/grad_kernel.hpp); the score model's N cotangents from the HIP score kernel
             params = [p for p in ctrl.parameters() if p.requires_grad]
@@ -199,7 +197,7 @@ class BaseOCLoss:
         fn = self._graphed.get(key)
         if fn is None:
             fn = _IntegralPass(ctrl)
-            if self.graph_training and type(ctrl).__name__ == "ClippedCtrl" and type(getattr(ctrl, "base_model", None)).__name__ == "FourierMLP":
+            if route == "graphed":
                 try:
                     sample = (t_unique.detach().clone(), xs.detach().clone(), zc.detach().clone())
                     fn = torch.cuda.make_graphed_callables(fn, sample)
@@ -235,15 +233,12 @@ class BaseOCLoss:
         with torch.enable_grad():
             xN = x_n.detach().requires_grad_(True)
             lam, = torch.autograd.grad((w * terminal(xN).view(B, 1)).sum(), xN)
-        ref_kind = E.resolve_reference(reference_ctrl) if reference_ctrl is not None else ("none", {})
-        if self.native_adjoint and E.adjoint_ctrl_ok(ctrl) and E.diagonal_reference(*ref_kind):
-            self.last_adjoint_path = "native"
-            grads = T.kl_grads_native(ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, ref_kind=ref_kind)
-        elif self.fused_training and type(ctrl).__name__ == "ClippedCtrl" and type(getattr(ctrl, "base_model", None)).__name__ == "FourierMLP":
-            self.last_adjoint_path = "fused"
+        self.last_adjoint_path = R.kl_route(self, reference_ctrl)
+        if self.last_adjoint_path == "native":
+            grads = T.kl_grads_native(ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, ref_kind=E.resolve_reference(reference_ctrl))
+        elif self.last_adjoint_path == "fused":
             grads = T.kl_grads_fused(ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, reference_ctrl=reference_ctrl)
         else:
-            self.last_adjoint_path = "stepwise"
             grads = T.kl_grads_stepwise(self, ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, reference_ctrl=reference_ctrl)
         return T.hand_to_autograd(self, value, params, grads)
 
@@ -285,15 +280,14 @@ class BaseOCLoss:
 
     def _coef(self, ts, device, **kw):
         # per-step gains of the control wrapper itself (LerpCtrl: g(t) and t/T; CancelDriftCtrl: drift/g and g/2), whatever the loss
-        ctrl, _ = E.unwrap_ctrl(self.generative_ctrl)
-        cname = type(ctrl).__name__
-        if cname in ("LerpCtrl", "CancelDriftCtrl") and kw.get("kind", self.kind) not in ("cmcd", "cmcd_eubo"):
-            if cname == "LerpCtrl":
+        rec = R.describe_ctrl(self.generative_ctrl)
+        if rec.kind in (L.CTRL_LERP, L.CTRL_CANCEL_DRIFT) and kw.get("kind", self.kind) not in ("cmcd", "cmcd_eubo"):
+            if rec.kind == L.CTRL_LERP:
                 kw.setdefault("lerp", True)
             else:
-                kw.setdefault("cancel", "rescale" if ctrl.use_rescaling else "plain")
-            if getattr(self, "_ctrl_sde_cpu", None) is None or self._ctrl_sde_cpu[0] is not ctrl.sde:
-                self._ctrl_sde_cpu = (ctrl.sde, E._cpu_sde(ctrl.sde))
+                kw.setdefault("cancel", "rescale" if rec.ctrl.use_rescaling else "plain")
+            if getattr(self, "_ctrl_sde_cpu", None) is None or self._ctrl_sde_cpu[0] is not rec.ctrl.sde:
+                self._ctrl_sde_cpu = (rec.ctrl.sde, E._cpu_sde(rec.ctrl.sde))
             kw["ctrl_sde"] = self._ctrl_sde_cpu[1]
         sde_cpu = self._sde_cpu()  # (may clear the cache)
         # the entry holds `ts` itself: while it is cached its address cannot be handed to another grid, so (address, version) is an
@@ -329,8 +323,7 @@ class BaseOCLoss:
                 res = None
         if res is None and terminal_unnorm_log_prob is not None:
             late.append((-1.0, terminal_unnorm_log_prob))
-            if ctrl_tgt is not None:
-                desc.target = E.dist_desc(ctrl_tgt, device, keep, score_only=True)
+            desc.target = E.dist_desc(ctrl_tgt, device, keep, score_only=True)  # (SDENG_DIST_NONE where the control has no target)
         if reference_log_prob is not None:
             rr = E.resolve_logp(reference_log_prob)
             ok = False
@@ -381,7 +374,7 @@ class BaseOCLoss:
         if desc.target.kind == L.DIST_GMM_FULL and (ref[0] != "none" or form == L.FORM_EUBO):
             raise E.UnsupportedByEngine("a full-covariance mixture target inside a Score / Lerp / CancelDrift control is evaluated in the kernel's "
                                         "reference slot: forward passes of the solvers without a reference drift (PIS / DDS / DIS) only")
-        _, lerp_prior = E.ctrl_target(ctrl)
+        desc.prior = E.dist_desc(E.ctrl_target(ctrl)[1], device, keep)  # a LerpCtrl's prior (SDENG_DIST_NONE without one), unless the kernel adds the initial log-density
         rnd0 = None
         if initial_log_prob is not None:
             pr = E.resolve_logp(initial_log_prob)
@@ -392,10 +385,6 @@ class BaseOCLoss:
                 desc.flags |= L.FLAG_INIT_LOGP
             except E.UnsupportedByEngine:
                 rnd0 = initial_log_prob if form == L.FORM_EUBO else initial_log_prob(x).view((-1, 1))  # EUBO: at the noised samples
-                if lerp_prior is not None:
-                    desc.prior = E.dist_desc(lerp_prior, device, keep)
-        elif lerp_prior is not None:
-            desc.prior = E.dist_desc(lerp_prior, device, keep)
         if self._perturb:  # log-variance training with sde_ctrl_noise / sde_ctrl_dropout (BaseOCLoss._lv_loss)
             coef_kw = dict(coef_kw or {}, **self._perturb)
             desc.flags |= (L.FLAG_CTRL_NOISE if "ctrl_noise" in self._perturb else 0) | (L.FLAG_CTRL_DROPOUT if "ctrl_dropout" in self._perturb else 0)
@@ -538,8 +527,7 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         desc.N = ts.numel() - 1
         desc.seed, desc.particle0 = int(self.seed), int(self.particle0)
         desc.net = E.net_desc(self._ctrl(use_ema), device, keep)
-        target = getattr(self.sde.target_score, "__self__", None)
-        prior = getattr(self.sde.prior_score, "__self__", None)
+        target, prior = R.self_of(self.sde.target_score), R.self_of(self.sde.prior_score)
         if target is None or prior is None:
             raise E.UnsupportedByEngine("ControlledLangevinSDE.target_score / prior_score must be bound Distribution.score methods")
         res = E.resolve_logp(terminal_unnorm_log_prob)
@@ -603,8 +591,7 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         log-variance training and by the cost pass of the KL adjoint."""
         M, B, d = xs.shape
         N = M - 1
-        target = getattr(self.sde.target_score, "__self__", None)
-        prior = getattr(self.sde.prior_score, "__self__", None)
+        target, prior = R.self_of(self.sde.target_score), R.self_of(self.sde.prior_score)
         flat = xs.reshape(M * B, d)
         _, s_tgt = E.dist_eval(target, flat, want_logp=False)
         _, s_pri = E.dist_eval(prior, flat, want_logp=False)
@@ -625,7 +612,7 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         g = float(self.sde.diff_coeff)
         b, s_tgt = self._cmcd_drifts(coef, xs)
         u = E.ctrl_forward_rows(fused_net_view(ctrl), coef[:, 0], xs)
-        if type(ctrl).__name__ == "ScoreCtrl":
+        if R.describe_ctrl(ctrl).own_kind == L.CTRL_SCORE:
             sc = ctrl.scale_score * _clip(s_tgt, ctrl.clip_score).view(M, B, d)
             if ctrl.score_model is not None:
                 sc = sc * ctrl.clipped_score_model(coef[:, 0].contiguous().view(-1, 1), None).view(M, 1, 1)
@@ -655,18 +642,15 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
             out = (w * (-terminal_unnorm_log_prob(xN).view(B, 1))).sum()
             lam = torch.autograd.grad(out, xN)[0] if out.requires_grad else torch.zeros_like(xN)
 
-        if self.native_adjoint and E.cmcd_adjoint_ok(self):
-            # ClippedCtrl / ScoreCtrl, diagonal or isotropic prior, mixture / phi^4 / logistic-regression target: the recursion over the
-            # N + 1 evaluation points is ONE launch (sdeng_cmcd_kl_adjoint); its input, the per-step cost cotangents, is one batched
-            # forward pass over the HIP states.  Parameter gradients from the per-row arrays, as in _kl_loss.
-            self.last_adjoint_path = "native"
+        self.last_adjoint_path = R.cmcd_kl_route(self)
+        if self.last_adjoint_path == "native":
+            # the kernel's input, the per-step cost cotangents, is one batched forward pass over the HIP states; parameter gradients as in _kl_loss
             coef = self._coef(ts, x.device)
             with torch.no_grad():
                 cbar, s_tgt = self._cmcd_step_costs(ctrl, coef, xs, z)
-            graphless = type(getattr(self.sde.target_score, "__self__", None)).__name__ in E._GRAPHLESS_SCORE
+            graphless = R.dist_kind(R.self_of(self.sde.target_score)) in R.GRAPHLESS_TARGETS
             arrays, _ = E.cmcd_kl_adjoint(ctrl, self.sde, coef, xs, cbar, w, lam, score_ext=s_tgt if graphless else None)
             return T.hand_to_autograd(self, value, params, T.param_grads(ctrl, coef[:, 0].contiguous(), arrays, N + 1, B, params))
-        self.last_adjoint_path = "stepwise"
         grads = [torch.zeros_like(p) for p in params]
 
         def step(lam_in, x_in, z_in, s, t, w_in):
@@ -687,7 +671,7 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
 
         tdev = ts.to(x.device)  # (the ~130 small kernels of a step are launch-bound, 2048 x 100: 5 ms per step: walk_adjoint replays them as a hipGraph)
         found = T.walk_adjoint(self, ("cmcd", id(ctrl), B, d, str(x.device)), step, grads, lam, lambda k: (xs[k], z[k], tdev[k], tdev[k + 1], w), N,
-                               self.graph_adjoint and _capturable(ctrl, self.sde.target_score))
+                               self.graph_adjoint and R.graph_capturable(ctrl, self.sde.target_score))
         return T.hand_to_autograd(self, value, params, found)
 
 
@@ -746,7 +730,7 @@ class TimeReversalLoss(_InitialLogProbLoss):
         if self.inference_ctrl is not None:
             raise E.UnsupportedByEngine("a learned inference control needs the divergence of a net (autograd): not on the HIP path")
         init = None if (train and self.method in ["kl", "kl_ito"]) else initial_log_prob
-        lerp = type(self.generative_ctrl).__name__ == "LerpCtrl"
+        lerp = R.describe_ctrl(self.generative_ctrl).own_kind == L.CTRL_LERP
         # quirk kept: TimeReversalLoss.simulate never uses the EMA net (losses/oc.py:1177-1180)
         return self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=init,
                               form=L.FORM_EM, flags=L.FLAG_ITO if compute_ito_int else 0, use_ema=False,
@@ -754,7 +738,7 @@ class TimeReversalLoss(_InitialLogProbLoss):
 
     def __call__(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None):
         """[TRAINING] losses/oc.py:1240-1272, log-variance methods, no inference control: cost <u, u.detach() - u/2> dt + <u, db>."""
-        lerp = type(self.generative_ctrl).__name__ == "LerpCtrl"
+        lerp = R.describe_ctrl(self.generative_ctrl).own_kind == L.CTRL_LERP
         kl = self.method in ("kl", "kl_ito")
         ito = self.method != "kl"  # :1251 compute_ito_int = self.method != "kl"
 

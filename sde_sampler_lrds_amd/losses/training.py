@@ -5,7 +5,9 @@ from __future__ import annotations
 
 import torch
 
+from .. import _lib as L
 from .. import engine as E
+from .. import routes as R
 
 
 def ctrl_batched(ctrl, t_unique: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -17,25 +19,26 @@ def ctrl_batched(ctrl, t_unique: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     M, B, d = x.shape
     flat = x.reshape(M * B, d)
     t_rows = t_unique.repeat_interleave(B).view(-1, 1)
-    name, net = type(ctrl).__name__, getattr(ctrl, "base_model", None)
-    if name not in ("ClippedCtrl", "ScoreCtrl", "LerpCtrl", "CancelDriftCtrl") or type(net).__name__ != "FourierMLP":
+    rec = R.describe_ctrl(ctrl)
+    if rec.own_kind is None or R.name_of(ctrl.base_model) != "FourierMLP":  # (a wrapped control is called as a whole)
         return ctrl(t_rows, flat)
+    kind, net = rec.kind, ctrl.base_model
     h = net.input_embed(flat) + net.timestep_embed(t_unique.view(-1, 1)).repeat_interleave(B, dim=0)
     for layer in net.hidden_layer:
         h = layer(net.activation(h))
     out = _clip(net.out_layer(net.activation(h)), ctrl.clip_model)
-    if name == "ClippedCtrl":
+    if kind == L.CTRL_CLIPPED:
         return out
-    if name in ("ScoreCtrl", "CancelDriftCtrl"):
-        score = ctrl.scale_score * ctrl.clipped_target_score(t_rows, flat)
-    else:
+    if kind == L.CTRL_LERP:
         score = ctrl.scale_score * ctrl.clipped_interpolated_score(t_rows, flat)
+    else:
+        score = ctrl.scale_score * ctrl.clipped_target_score(t_rows, flat)
     if ctrl.score_model is not None:
         score = score * _clip(ctrl.score_model(t_unique.view(-1, 1)), ctrl.clip_model).repeat_interleave(B, dim=0)
-    if name == "CancelDriftCtrl":  # reparam.py:142-145
+    if kind == L.CTRL_CANCEL_DRIFT:  # reparam.py:142-145
         g, f = ctrl.sde.diff(t_rows, flat), ctrl.sde.drift(t_rows, flat)
         return out + (f / g) + 0.5 * g * score if ctrl.use_rescaling else out + (f / torch.square(g)) + 0.5 * score
-    return out + (ctrl.sde.diff(t_rows, flat) * score if name == "LerpCtrl" else score)
+    return out + (ctrl.sde.diff(t_rows, flat) * score if kind == L.CTRL_LERP else score)
 
 
 class _FusedIntegral(torch.autograd.Function):
@@ -71,27 +74,12 @@ class _FusedIntegral(torch.autograd.Function):
 
 
 _NET_VIEWS = {}
-
-
-def fused_training_ok(ctrl) -> bool:
-    """Controls whose batched log-variance pass is the fused HIP forward + backward: ClippedCtrl over a FourierMLP, and a plain ScoreCtrl
-    over one (its score part has no state gradient to take in this pass) on a target the score kernel knows."""
-    if type(getattr(ctrl, "base_model", None)).__name__ != "FourierMLP":
-        return False
-    if type(ctrl).__name__ == "ClippedCtrl":
-        return True
-    if type(ctrl).__name__ != "ScoreCtrl" or not (ctrl.score_model is None or type(ctrl.score_model).__name__ == "TimeEmbed"):
-        return False
-    try:
-        E.dist_desc(E.ctrl_target(ctrl)[0], "cpu", [])
-    except E.UnsupportedByEngine:
-        return False
-    return True
+fused_training_ok, _capturable = R.lv_fused, R.graph_capturable  # (the names they have here)
 
 
 def fused_net_view(ctrl):
     """The ClippedCtrl part of a ScoreCtrl (same drift net, same clip) as sdeng_ctrl_vjp wants it; a ClippedCtrl is its own view."""
-    if type(ctrl).__name__ == "ClippedCtrl":
+    if R.describe_ctrl(ctrl).own_kind == L.CTRL_CLIPPED:
         return ctrl
     view = _NET_VIEWS.get(id(ctrl))
     if view is None or view[0]() is not ctrl or view[1].clip_model != ctrl.clip_model:
@@ -215,8 +203,7 @@ def walk_adjoint(loss, key, step, grads, lam, rest, N, graph):
 
 # ---- the three adjoints of BaseOCLoss._kl_loss: each -> the gradients, ordered as ``params`` -------------------------------------------------
 def kl_grads_native(ctrl, params, coef, xs, z, w, lam, *, lin, ito, ref_kind):
-    """ClippedCtrl (every RDS / LRDS solver at its defaults) or a Score / Lerp / CancelDrift control on a diagonal mixture, phi^4 or logistic-regression
-    target (DDS / PIS / DIS, BASELINE config 1), no / a diagonal reference: the whole recursion is ONE launch (sdeng_kl_adjoint: lambda in registers, u
+    """A control ``routes.kl_native`` accepts, no / a diagonal reference: the whole recursion is ONE launch (sdeng_kl_adjoint: lambda in registers, u
     recomputed, closed-form Hessian-vector products); the parameter gradients come from the per-row arrays, as in log-variance training."""
     N, B = xs.shape[0] - 1, xs.shape[1]
     arrays, _ = E.kl_adjoint(ctrl, coef, xs[:-1], z if ito else None, w, lam, lin=lin, ito=ito, ref=ref_kind)
@@ -275,17 +262,7 @@ def kl_grads_stepwise(loss, ctrl, params, coef, xs, z, w, lam, *, lin, ito, refe
 
     N, B, d = xs.shape[0] - 1, xs.shape[1], xs.shape[2]
     key = ("kl", id(ctrl), id(getattr(reference_ctrl, "__self__", reference_ctrl)), B, d, bool(lin), bool(ito), str(xs.device))
-    return walk_adjoint(loss, key, step, grads, lam, lambda k: (xs[k], z[k], coef[k], w), N, loss.graph_adjoint and _capturable(ctrl))
-
-
-def _capturable(ctrl, *score_fns) -> bool:
-    """Can one adjoint step of this control be captured as a hipGraph?  Not when a score in it is the base class's autograd evaluation
-    (distr/base.py:146-154: a nested torch.autograd.grad on a freshly flagged leaf -- LogisticRegression): capture refuses it."""
-    fns = list(score_fns)
-    inner = getattr(ctrl, "score", ctrl)  # RemoveReferenceCtrl wraps the score control
-    if hasattr(inner, "target_score"):
-        fns.append(inner.target_score)
-    return all(type(getattr(f, "__self__", None)).__name__ not in E._GRAPHLESS_SCORE for f in fns)
+    return walk_adjoint(loss, key, step, grads, lam, lambda k: (xs[k], z[k], coef[k], w), N, loss.graph_adjoint and R.graph_capturable(ctrl))
 
 
 def _graphed_step(loss, key, step, grads, example):
