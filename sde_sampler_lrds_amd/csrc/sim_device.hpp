@@ -27,13 +27,22 @@ SD_INLINE float clampf(float v, float m) {
   return v;
 }
 
-// torch.clip of one feature tile with a bound that almost never binds (1e4 / 1e5 in every config): one compare per element into
-// a wave-wide mask, and the 4-instruction NaN-preserving clamp only when some lane is out of range or NaN
+// max(m, |v[0]|, .., |v[3]|) as a tree of three-operand maxima (v_max3_f32 with |.| operand modifiers): half an instruction per
+// element.  A NaN element is DROPPED (fmaxf returns the other operand); the result is NaN only when everything was.
+SD_INLINE float absmax_tile(const f32x4& v) {
+  return __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), __builtin_fabsf(v[2])), __builtin_fabsf(v[3]));
+}
+SD_INLINE float absmax_tile(float m, const f32x4& v) {
+  m = __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(v[0])), __builtin_fabsf(v[1]));
+  return __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(v[2])), __builtin_fabsf(v[3]));
+}
+
+// torch.clip of one feature tile with a bound that almost never binds (1e4 / 1e5 in every config): the tile's largest |v| against
+// the bound into a wave-wide mask, and the 4-instruction NaN-preserving clamp only when some lane is out of range.  The maximum
+// drops NaN elements, so a lane whose only offenders are NaNs no longer trips the test -- and keeps the values it would have had:
+// clampf leaves a NaN a NaN and an in-range value alone (tests/test_clip_tree_cpu.py holds the two forms to each other bit for bit).
 SD_INLINE void clamp_tile_rare(f32x4& v, float m) {
-  bool out_of_range = false;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) out_of_range |= !(__builtin_fabsf(v[r]) <= m);
-  if (__builtin_amdgcn_ballot_w64(out_of_range) != 0) {
+  if (__builtin_amdgcn_ballot_w64(!(absmax_tile(v) <= m)) != 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = clampf(v[r], m);
   }

@@ -589,14 +589,13 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
           }
         }
         if (a.clip_model > 0.0f) {
-          // ClippedCtrl's clip (reparam.py:42) almost never binds (clip_model = 1e4): one compare per element into a
-          // wave-wide mask, and the 4-instruction NaN-preserving clamp only when some lane is out of range or NaN
-          bool out_of_range = false;
+          // ClippedCtrl's clip (reparam.py:42) almost never binds (clip_model = 1e4): the group's largest |u| (absmax_tile: half an
+          // instruction per element) against the bound into a wave-wide mask, and the 4-instruction NaN-preserving clamp only when
+          // some lane is out of range.  NaN elements drop out of the maximum; the clamp would have left them as they are.
+          float umax = absmax_tile(u[0]);
 #pragma unroll
-          for (int o = 0; o < OT; ++o)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out_of_range |= !(__builtin_fabsf(u[o][r]) <= a.clip_model);
-          if (__builtin_amdgcn_ballot_w64(out_of_range) != 0) {
+          for (int o = 1; o < OT; ++o) umax = absmax_tile(umax, u[o]);
+          if (__builtin_amdgcn_ballot_w64(!(umax <= a.clip_model)) != 0) {
 #pragma unroll
             for (int o = 0; o < OT; ++o)
 #pragma unroll
