@@ -1,4 +1,4 @@
-"""ctypes binding of libsdeng.so (the C ABI of include/sdeng.h).
+"""ctypes binding of libsdeng.so, derived from include/sdeng.h (the C ABI) when this module is imported.
 
 There is no CPU fallback: if the HIP library is missing or fails to load, importing this module's
 ``lib()`` raises.  ``python -m sde_sampler_lrds_amd.build`` (or ``__graft_entry__.build()``) builds it.
@@ -7,84 +7,80 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
-ABI_VERSION = 4
-NCOEF = 16
-
-FORM_LIN, FORM_EM, FORM_CMCD, FORM_EUBO, FORM_CMCD_EUBO = 0, 1, 2, 3, 4
-FLAG_ITO, FLAG_INIT_LOGP, FLAG_TERM_REF, FLAG_TERM_TARGET, FLAG_SPLIT_TILES, FLAG_REMOVE_REF, FLAG_REUSE_PACK = 1, 2, 4, 8, 16, 32, 64
-FLAG_CTRL_NOISE, FLAG_CTRL_DROPOUT = 128, 256  # sde_ctrl_noise / sde_ctrl_dropout of log-variance training (sdeng.h)
 SPLIT_TILES_MAX_B = 8192  # SDENG_FLAG_SPLIT_TILES is honoured up to this batch size (sdeng.h, sdeng_api.hip split_eligible)
-(DIST_NONE, DIST_GMM_DIAG, DIST_GAUSS_DIAG, DIST_ISO_GAUSS, DIST_PHI4, DIST_LOGREG, DIST_GAUSS_FULL, DIST_RINGS, DIST_GMM_FULL,
- DIST_CHECKERBOARD) = range(10)
-CTRL_CLIPPED, CTRL_SCORE, CTRL_LERP, CTRL_NONE, CTRL_CANCEL_DRIFT = 0, 1, 2, 3, 4
-REF_NONE, REF_GAUSS_DIAG, REF_GMM_DIAG, REF_GMM_FULL = 0, 1, 2, 3
 
-TILT_DOT, TILT_SQ_NORM, TILT_SUM = 0, 1, 2
-
-E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = -1, -2, -3, -4
-
-_fp = C.c_void_p  # device pointers travel as integers
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+_DIRECTIVE = re.compile(r"#(?:ifndef SDENG_H|include <\w+\.h>|endif|define SDENG_(\w+)(.*))\s*")
+_DECLARATION = re.compile(r"\s*(?:typedef\s+struct\s+(sdeng_\w+)\s*\{(.*?)\}\s*\1\s*;"  # a structure ...
+                          r"|([\w\s*]+?)\b(sdeng_\w+)\s*\(([^()]*)\)\s*;)", re.S)  # ... or a prototype
 
 
-class Dist(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("loc", _fp), ("scale", _fp), ("w", _fp),
-                ("p0", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("p3", C.c_float), ("clip", C.c_float), ("aux", _fp)]
+def _refuse(what, text):
+    raise ImportError(f"include/sdeng.h: {what}: {' '.join(text.split())[:120]!r}")
 
 
-class TimeEmbed(C.Structure):
-    _fields_ = [("coeff", _fp), ("phase", _fp), ("w", _fp * 4), ("b", _fp * 4), ("n_hidden", C.c_int32),
-                ("dim_out", C.c_int32), ("w_out", _fp), ("b_out", _fp)]
+def _declarators(decl, structs, param=False):
+    """``[(name, ctype)]`` of one field declaration or of one parameter: a base type, then declarators that each carry their own ``*``
+    and ``[n]``.  A pointer is a c_void_p (device pointers travel as integers) unless it is a parameter that points to a structure."""
+    head, rest = re.fullmatch(r"([\w\s]*)(.*)", decl, re.S).groups()
+    words = [w for w in head.split() if w != "const"]
+    if words and not rest.startswith("*"):
+        rest = words.pop() + rest  # no star before the first name: the head's last word is that name, not part of the type
+    base = " ".join(words)
+    out = []
+    for piece in rest.split(","):
+        m = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*", piece)
+        if m is None or (param and m[3]):
+            _refuse(f"cannot parse the declarator {piece.strip()!r}", decl)
+        if m[1]:
+            ctype = C.POINTER(structs[base]) if param and base in structs else C.c_void_p
+        else:
+            ctype = _SCALARS.get(base) or structs.get(base) or _refuse(f"unknown type {base!r}", decl)
+        out.append((m[2], ctype * int(m[3]) if m[3] else ctype))
+    return out
 
 
-class Net(C.Structure):
-    _fields_ = [("ctrl_kind", C.c_int32), ("reserved", C.c_int32),
-                ("w_in", _fp), ("b_in", _fp), ("w_h1", _fp), ("b_h1", _fp), ("w_h2", _fp), ("b_h2", _fp),
-                ("w_out", _fp), ("b_out", _fp), ("t_embed", TimeEmbed), ("score_model", TimeEmbed),
-                ("clip_model", C.c_float), ("clip_score", C.c_float), ("scale_score", C.c_float), ("reserved_f", C.c_float)]
+def read_header(text: str):
+    """The declarations of include/sdeng.h, each kind in header order: constants ``{NAME: int}`` (the SDENG_ prefix dropped), structures
+    ``{sdeng_name: ctypes.Structure}`` and prototypes ``{sdeng_name: (restype, argtypes)}``.  Not a C parser: it knows the constructs the
+    header uses and raises ImportError, quoting the text, on anything else -- a declaration skipped in silence would be a binding that
+    disagrees with the library."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)  # comments first: they hold prototype-like text
+    text = re.sub(r"^#ifdef __cplusplus\n.*?^#endif\n", "", text, flags=re.S | re.M)  # the two halves of extern "C" { }
+    consts, structs, protos = {}, {}, {}
+    for line in re.findall(r"^[ \t]*#.*$", text, re.M):
+        m = _DIRECTIVE.fullmatch(line) or _refuse("unknown directive", line)
+        if m[1] and (m[1], m[2].strip()) != ("H", ""):  # SDENG_H without a value is the include guard
+            expr = re.sub(r"\b(\d+)(?:ull|u)\b", r"\1", m[2])
+            try:  # decimal literals, parentheses, unary minus and <<: nothing else reaches eval
+                consts[m[1]] = int(eval(re.fullmatch(r"(?:\d+|<<|[\s()-])+", expr)[0]))
+            except (SyntaxError, TypeError):  # TypeError: no match, or an empty pair of parentheses
+                _refuse("not an integer expression", line)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    pos = 0
+    while text[pos:].strip():
+        m = _DECLARATION.match(text, pos) or _refuse("cannot parse the declaration", text[pos:])
+        pos = m.end()
+        if m[1]:
+            fields = [f for decl in m[2].split(";") if decl.strip() for f in _declarators(decl, structs)]
+            camel = "".join(part.capitalize() for part in m[1].split("_")[1:])  # sdeng_time_embed -> TimeEmbed
+            structs[m[1]] = type(camel, (C.Structure,), {"_fields_": fields})
+        else:
+            restype = _RETURNS.get(" ".join(m[3].split())) or _refuse("unknown return type", m[0])
+            params = [] if m[5].strip() == "void" else [_declarators(p, structs, param=True)[0] for p in m[5].split(",")]
+            protos[m[4]] = (restype, [ctype for _, ctype in params])
+    return consts, structs, protos
 
 
-class Ref(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("means_init", _fp), ("vars_init", _fp), ("weights", _fp), ("eigvecs", _fp),
-                ("shared_var", C.c_int32), ("reserved", C.c_int32)]
-
-
-class Adjoint(C.Structure):  # sdeng_adjoint (include/sdeng.h)
-    _fields_ = [(n, C.c_void_p) for n in ("xs", "noise", "w", "lam_in", "lam_out", "a0", "a1", "a2", "d0", "d1", "d2", "dout", "dst")] + [
-        ("detach_score", C.c_int32), ("score", C.c_void_p)]
-
-
-class CmcdAdjoint(C.Structure):  # sdeng_cmcd_adjoint (include/sdeng.h)
-    _fields_ = [(n, C.c_void_p) for n in ("xs", "cbar", "w", "lam_in", "lam_out", "a0", "a1", "a2", "d0", "d1", "d2", "dout", "dst")] + [
-        ("detach_score", C.c_int32), ("score", C.c_void_p)]
-
-
-class Desc(C.Structure):
-    _fields_ = [("abi_version", C.c_int32), ("form", C.c_int32), ("flags", C.c_uint32),
-                ("B", C.c_int32), ("d", C.c_int32), ("N", C.c_int32),
-                ("particle0", C.c_int64), ("seed", C.c_uint64),
-                ("coef", _fp), ("x_in", _fp), ("x_out", _fp), ("rnd_out", _fp), ("xs_out", _fp), ("noise_in", _fp),
-                ("net", Net), ("ref", Ref), ("target", Dist), ("ref_dist", Dist), ("prior", Dist),
-                ("cmcd_g", C.c_float), ("cmcd_clip", C.c_float), ("workspace", _fp), ("workspace_bytes", C.c_size_t),
-                ("ev_start", _fp), ("ev_stop", _fp), ("x0_dist", Dist), ("x0_out", _fp)]
-
-
-class SinkhornResult(C.Structure):  # sdeng_sinkhorn_result (include/sdeng.h)
-    _fields_ = [("distance", C.c_double), ("max_err_u", C.c_double), ("max_err_v", C.c_double), ("iters", C.c_int32),
-                ("materialised", C.c_int32)]
-
-
-class Tilted(C.Structure):  # sdeng_tilted (include/sdeng.h)
-    _fields_ = [("abi_version", C.c_int32), ("flags", C.c_uint32)] + \
-        [(n, C.c_int32) for n in ("M", "n_times", "rows_per_time", "d", "k", "full_cov", "num_layers", "channels", "tilt_type",
-                                  "use_scaling_factor", "use_s_t_scaling", "reserved")] + \
-        [("x", _fp), ("tinfo", _fp), ("w_in", _fp), ("b_in", _fp), ("w_h", _fp * 4), ("b_h", _fp * 4)] + \
-        [(n, _fp) for n in ("w_out", "b_out", "te_coeff", "te_phase", "te_w1", "te_b1", "te_w2", "te_b2", "mean_gauss", "var_gauss",
-                            "weights", "means", "vars", "eigvecs", "log_prob", "grad", "workspace")] + [("workspace_bytes", C.c_size_t)]
-
-
-class TiltedRows(C.Structure):  # sdeng_tilted_rows (include/sdeng.h)
-    _fields_ = [("a", _fp * 5), ("d", _fp * 5), ("xs", _fp), ("dv", _fp)]
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "sdeng.h")) as _f:
+    _CONSTS, _STRUCTS, _PROTOS = read_header(_f.read())  # once per process
+globals().update(_CONSTS)  # ABI_VERSION, NCOEF, FORM_*, FLAG_*, DIST_*, CTRL_*, REF_*, TILT_*, E_*, ...
+globals().update({cls.__name__: cls for cls in _STRUCTS.values()})  # Dist, TimeEmbed, Net, Ref, Desc, Adjoint, CmcdAdjoint, ...
+EXPORTS = list(_PROTOS)
 
 
 class EngineError(RuntimeError):
@@ -95,14 +91,6 @@ class EngineError(RuntimeError):
 
 _LIB = None
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsdeng.so")
-
-EXPORTS = ["sdeng_abi_version", "sdeng_last_error", "sdeng_workspace_bytes", "sdeng_simulate", "sdeng_logz",
-           "sdeng_logz_workspace_bytes", "sdeng_ctrl_forward", "sdeng_dist_eval", "sdeng_dist_workspace_bytes",
-           "sdeng_philox_normal", "sdeng_philox_normal_steps", "sdeng_sample_x0", "sdeng_ctrl_vjp", "sdeng_ctrl_vjp_workspace_bytes",
-           "sdeng_langevin_moves", "sdeng_langevin_moves_workspace_bytes", "sdeng_kl_adjoint", "sdeng_kl_adjoint_workspace_bytes",
-           "sdeng_sinkhorn", "sdeng_sinkhorn_workspace_bytes", "sdeng_mmd_median", "sdeng_mmd_median_workspace_bytes",
-           "sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes", "sdeng_rwmh_moves", "sdeng_rwmh_moves_workspace_bytes",
-           "sdeng_tilted_eval", "sdeng_tilted_eval_workspace_bytes", "sdeng_tilted_vjp", "sdeng_tilted_vjp_workspace_bytes"]
 
 
 def lib() -> C.CDLL:
@@ -115,67 +103,9 @@ def lib() -> C.CDLL:
     import torch  # noqa: F401 -- before the library: libsdeng.so then binds to the HIP runtime torch has loaded (its own copy), instead
     #                          of bringing /opt/rocm's into the process first; with two runtimes the library's launches find no device
     L = C.CDLL(LIB_PATH)
-    L.sdeng_abi_version.restype = C.c_int
-    L.sdeng_last_error.restype = C.c_char_p
-    L.sdeng_workspace_bytes.restype = C.c_size_t
-    L.sdeng_workspace_bytes.argtypes = [C.POINTER(Desc)]
-    L.sdeng_simulate.restype = C.c_int
-    L.sdeng_simulate.argtypes = [C.POINTER(Desc), C.c_void_p]
-    L.sdeng_logz.restype = C.c_int
-    L.sdeng_logz.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.sdeng_logz_workspace_bytes.restype = C.c_size_t
-    L.sdeng_ctrl_forward.restype = C.c_int
-    L.sdeng_ctrl_forward.argtypes = [C.POINTER(Desc), C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sdeng_dist_eval.restype = C.c_int
-    L.sdeng_dist_eval.argtypes = [C.POINTER(Dist), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_size_t, C.c_void_p]
-    L.sdeng_dist_workspace_bytes.restype = C.c_size_t
-    L.sdeng_dist_workspace_bytes.argtypes = [C.POINTER(Dist), C.c_int32]
-    L.sdeng_philox_normal.restype = C.c_int
-    L.sdeng_philox_normal.argtypes = [C.c_uint64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.sdeng_philox_normal_steps.restype = C.c_int
-    L.sdeng_philox_normal_steps.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
-    L.sdeng_sample_x0.restype = C.c_int
-    L.sdeng_sample_x0.argtypes = [C.POINTER(Dist), C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    L.sdeng_ctrl_vjp.restype = C.c_int
-    L.sdeng_ctrl_vjp.argtypes = [C.POINTER(Desc), C.c_int32, C.c_int32] + [C.c_void_p] * 12
-    L.sdeng_kl_adjoint.restype = C.c_int
-    L.sdeng_kl_adjoint.argtypes = [C.POINTER(Desc), C.POINTER(Adjoint), C.c_void_p]
-    L.sdeng_kl_adjoint_workspace_bytes.restype = C.c_size_t
-    L.sdeng_kl_adjoint_workspace_bytes.argtypes = [C.POINTER(Desc)]
-    L.sdeng_cmcd_kl_adjoint.restype = C.c_int
-    L.sdeng_cmcd_kl_adjoint.argtypes = [C.POINTER(Desc), C.POINTER(CmcdAdjoint), C.c_void_p]
-    L.sdeng_cmcd_kl_adjoint_workspace_bytes.restype = C.c_size_t
-    L.sdeng_cmcd_kl_adjoint_workspace_bytes.argtypes = [C.POINTER(Desc)]
-    L.sdeng_ctrl_vjp_workspace_bytes.restype = C.c_size_t
-    L.sdeng_ctrl_vjp_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.sdeng_langevin_moves.restype = C.c_int
-    L.sdeng_langevin_moves.argtypes = [C.POINTER(Dist), C.POINTER(Dist), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float] + \
-        [C.c_void_p] * 7 + [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.sdeng_langevin_moves_workspace_bytes.restype = C.c_size_t
-    L.sdeng_langevin_moves_workspace_bytes.argtypes = [C.POINTER(Dist), C.POINTER(Dist), C.c_int32]
-    L.sdeng_rwmh_moves.restype = C.c_int
-    L.sdeng_rwmh_moves.argtypes = [C.POINTER(Dist), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5 + \
-        [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.sdeng_rwmh_moves_workspace_bytes.restype = C.c_size_t
-    L.sdeng_rwmh_moves_workspace_bytes.argtypes = [C.POINTER(Dist), C.c_int32]
-    L.sdeng_sinkhorn.restype = C.c_int
-    L.sdeng_sinkhorn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double] + \
-        [C.c_void_p] * 6 + [C.POINTER(SinkhornResult), C.c_void_p, C.c_size_t, C.c_void_p]
-    L.sdeng_sinkhorn_workspace_bytes.restype = C.c_size_t
-    L.sdeng_sinkhorn_workspace_bytes.argtypes = [C.c_int32] * 4
-    L.sdeng_mmd_median.restype = C.c_int
-    L.sdeng_mmd_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.sdeng_mmd_median_workspace_bytes.restype = C.c_size_t
-    L.sdeng_mmd_median_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.sdeng_tilted_eval.restype = C.c_int
-    L.sdeng_tilted_eval.argtypes = [C.POINTER(Tilted), C.c_void_p]
-    L.sdeng_tilted_eval_workspace_bytes.restype = C.c_size_t
-    L.sdeng_tilted_eval_workspace_bytes.argtypes = [C.POINTER(Tilted)]
-    L.sdeng_tilted_vjp.restype = C.c_int
-    L.sdeng_tilted_vjp.argtypes = [C.POINTER(Tilted), C.POINTER(TiltedRows), C.c_void_p]
-    L.sdeng_tilted_vjp_workspace_bytes.restype = C.c_size_t
-    L.sdeng_tilted_vjp_workspace_bytes.argtypes = [C.POINTER(Tilted)]
+    for name, (restype, argtypes) in _PROTOS.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.sdeng_abi_version() != ABI_VERSION:
         raise ImportError(f"libsdeng.so ABI {L.sdeng_abi_version()} != binding ABI {ABI_VERSION}")
     _LIB = L

@@ -511,6 +511,14 @@ def _stream_ptr(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _check_supported(rc: int):
+    """``L.check`` for the entry points whose callers are told of a combination the library has no kernel for (INTEGRATION.md "Limits,
+    first") by the documented exception: E_UNSUPPORTED becomes UnsupportedByEngine with the library's reason."""
+    if rc == L.E_UNSUPPORTED:
+        raise UnsupportedByEngine(L.lib().sdeng_last_error().decode())
+    L.check(rc)
+
+
 def require_gpu(x: torch.Tensor):
     if not x.is_cuda:
         raise RuntimeError("the sdeng simulate path runs on an MI355X only: move the solver to a cuda device "
@@ -550,10 +558,7 @@ def run(desc: L.Desc, x: torch.Tensor, keep: list, return_traj=False, noise=None
     desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
     if events is not None:
         desc.ev_start, desc.ev_stop = events.start, events.stop
-    rc = lib.sdeng_simulate(C.byref(desc), _stream_ptr(device))
-    if rc == L.E_UNSUPPORTED:  # a combination the library has no kernel for (INTEGRATION.md "Limits, first"): the documented exception, its reason
-        raise UnsupportedByEngine(lib.sdeng_last_error().decode())
-    L.check(rc)
+    _check_supported(lib.sdeng_simulate(C.byref(desc), _stream_ptr(device)))
     return x_out, rnd, xs
 
 
@@ -1144,10 +1149,7 @@ def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
         launch = lambda: lib.sdeng_tilted_eval(C.byref(d), _stream_ptr(device))  # noqa: E731
         need = lib.sdeng_tilted_eval_workspace_bytes(C.byref(d))
     if need == 0:
-        rc = launch()  # the descriptor is rejected: fetch the code and the reason
-        if rc == L.E_UNSUPPORTED:
-            raise UnsupportedByEngine(lib.sdeng_last_error().decode())
-        L.check(rc)
+        _check_supported(launch())  # the descriptor is rejected: fetch the code and the reason
     versions = _tilted_versions(net, device)
     hit = _TILTED_PACKS.get(net)
     if hit is not None and hit[0] == versions and hit[1].numel() >= need:
@@ -1156,10 +1158,7 @@ def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
         ws = torch.empty(need, dtype=torch.uint8, device=device)
         _TILTED_PACKS[net] = (versions, ws)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    rc = launch()
-    if rc == L.E_UNSUPPORTED:
-        raise UnsupportedByEngine(lib.sdeng_last_error().decode())
-    L.check(rc)
+    _check_supported(launch())
     return logp, grad, arrays, (n_times, B, tdev[:, 0])
 
 

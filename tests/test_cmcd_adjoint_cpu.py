@@ -1,8 +1,6 @@
-"""Host side of the one-launch CMCD KL adjoint (no GPU): the exports, the algebra of the recursion over the N + 1 evaluation points, the
+"""Host side of the one-launch CMCD KL adjoint (no GPU): the descriptor's fields, the algebra of the recursion over the N + 1 evaluation points, the
 predicate that routes a loss to it, and what the C entry point refuses before any launch."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -20,19 +18,10 @@ from sde_sampler_lrds_amd.models.mlp import FourierMLP, TimeEmbed
 from sde_sampler_lrds_amd.models.reparam import ClippedCtrl, LerpCtrl, ScoreCtrl
 from tests import cmcd_adjoint_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def test_new_exports_are_declared_listed_and_built():
-    header = open(os.path.join(ROOT, "include", "sdeng.h")).read()
-    assert L.ABI_VERSION == 4 and re.search(r"#define SDENG_ABI_VERSION 4\b", header)
-    for sym in ("sdeng_cmcd_kl_adjoint", "sdeng_cmcd_kl_adjoint_workspace_bytes"):
-        assert re.search(r"\b" + sym + r"\(", header), sym
-        assert sym in L.EXPORTS
-        assert hasattr(L.lib(), sym)
-    assert "typedef struct sdeng_cmcd_adjoint" in header
+def test_cmcd_adjoint_has_the_fields_the_engine_fills():
+    """engine.cmcd_kl_adjoint sets these by name (that the entry points are declared, bound and built is tests/test_abi_cpu.py's)."""
     assert [n for n, _ in L.CmcdAdjoint._fields_] == ["xs", "cbar", "w", "lam_in", "lam_out", "a0", "a1", "a2", "d0", "d1", "d2", "dout", "dst", "detach_score", "score"]
-    assert L.lib().sdeng_abi_version() == 4
 
 
 def _mlp(d):

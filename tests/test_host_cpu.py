@@ -1,9 +1,7 @@
-"""CPU-only checks of the host side: the C-ABI library loads and exports every symbol of include/sdeng.h
-(no compute without a GPU), the descriptor compiler and coefficient tables, the API surface of the loss
+"""CPU-only checks of the host side: the C-ABI library loads and validates descriptors (no compute without a GPU; the binding itself
+is held to include/sdeng.h by tests/test_abi_cpu.py), the descriptor compiler and coefficient tables, the API surface of the loss
 classes, and that there is no CPU execution path."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -12,28 +10,6 @@ from sde_sampler_lrds_amd import _lib as L
 from sde_sampler_lrds_amd import engine as E
 from tests import build_cases as bc
 from tests import golden_cases as gc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def test_library_exports_every_declared_symbol():
-    header = open(os.path.join(ROOT, "include", "sdeng.h")).read()
-    declared = set(re.findall(r"\b(sdeng_[a-z0-9_]+)\s*\(", header))
-    assert declared, "no declarations parsed"
-    lib = ctypes.CDLL(L.LIB_PATH)
-    for sym in sorted(declared):
-        assert hasattr(lib, sym), f"{sym} declared in include/sdeng.h but not exported"
-    assert set(L.EXPORTS) <= declared
-    lib.sdeng_abi_version.restype = ctypes.c_int
-    assert lib.sdeng_abi_version() == L.ABI_VERSION
-
-
-def test_struct_sizes_match_header_layout():
-    # sizes the C compiler produces for the same field lists (checked once with hipcc: see DESIGN.md)
-    assert ctypes.sizeof(L.Dist) == 64
-    assert ctypes.sizeof(L.TimeEmbed) == 104
-    assert ctypes.sizeof(L.Ref) == 48
-    assert ctypes.sizeof(L.Net) == 296 and ctypes.sizeof(L.Desc) == 736  # gcc on include/sdeng.h (ABI 3)
 
 
 def test_workspace_bytes_and_bad_descriptors_without_gpu():
