@@ -529,6 +529,38 @@ typedef struct sdeng_tilted_rows { float *a[5], *d[5]; float *xs, *dv; } sdeng_t
 int sdeng_tilted_vjp(const sdeng_tilted* desc, const sdeng_tilted_rows* rows, void* stream);
 size_t sdeng_tilted_vjp_workspace_bytes(const sdeng_tilted* desc);
 
+/* Annealed samplers over an energy-based reference: n_moves Langevin moves of M chains in ONE launch -- mala_step / ula_step of
+ * additions/mcmc.py:77-135, 189-221 with the per-chain step-size heuristic of :55-74 (target_acceptance > 0), exactly the moves of
+ * sdeng_langevin_moves, with the density of sdeng_tilted_eval at every proposal: what re_sampler does swap_frequency - 1 times between two
+ * swap steps, smc_sampler n_warmup + n_mcmc times per level and MaximumLikelihoodEBM.cd_sampling from the positives
+ * (additions/ebm_mle.py:120-160, 340-380, 440-446, 505-540), one sdeng_tilted_eval launch and a dozen small host kernels per move.
+ * `desc` carries the net, the prior and the row-to-time layout (M, n_times, rows_per_time, tinfo: chain r moves at time r / rows_per_time;
+ * n_times = M, rows_per_time = 1 gives every chain its own time), the workspace and SDENG_FLAG_REUSE_PACK; its x, log_prob and grad are
+ * ignored.  State in / out: x [M,d], lp [M] = log_prob at x, grad [M,d] = its score, step [M].  Per move and chain:
+ *     prop = sqrt(2 step) z + (x + step grad);   (lp', grad') = sdeng_tilted_eval at (t, prop);
+ *     log_acc = (lp' + |prop - x - step grad|^2 / (4 step)) - (lp + |x - prop - step grad'|^2 / (4 step));  accepted iff log(u) < log_acc
+ * (a NaN lp' is a rejection: the chain keeps its state; the unadjusted move accepts always and reads no u), then the step heuristic.
+ * The time embedding of the net depends on the chain's time alone and is computed once per launch, not per move.
+ * Noise: injected normals z [n_moves,M,d] and uniforms u [n_moves,M], both or neither (unadjusted: z alone) -- or NULL: Philox stream 8
+ * for the normals (the counter layout of the step noise, keyed by (seed, chain0 + chain, move): sdeng_philox_normal_steps(...,
+ * stream_id = 8) replays them) and stream 9 for the uniforms (counter (chain0 + chain, 0, move, 9), output word 0).  Streams 0-7 are taken.
+ * samples (optional) [n_moves - keep_from, M, d], acc_sum (optional) [M], acc_last (optional) [M]: as sdeng_langevin_moves.
+ * Errors, all before any launch: SDENG_E_INVALID for what sdeng_tilted_eval rejects in the descriptor (but its three ignored pointers), a
+ * null `mv` or state pointer, n_moves < 0, keep_from outside [0, n_moves], exactly one of z / u for an adjusted move; SDENG_E_UNSUPPORTED
+ * as sdeng_tilted_eval; SDENG_E_WORKSPACE.  Workspace (sdeng_tilted_moves_workspace_bytes): the packed images where sdeng_tilted_eval
+ * keeps them (the three entry points share them), per-wave slots of six layers (the five pre-activations and the time embedding), then
+ * the proposal and proposal-score rows, 2 x [M,d]. */
+typedef struct sdeng_tilted_moves_state {
+  int32_t n_moves, keep_from, unadjusted, reserved;
+  float target_acceptance;          /* <= 0: steps stay fixed */
+  float *x, *lp, *grad, *step;      /* [M,d], [M], [M,d], [M]: in and out */
+  const float *z, *u;               /* injected noise or NULL (Philox 8 / 9) */
+  uint64_t seed; int64_t chain0;
+  float *samples, *acc_sum, *acc_last;   /* optional, as sdeng_langevin_moves */
+} sdeng_tilted_moves_state;
+int sdeng_tilted_moves(const sdeng_tilted* desc, const sdeng_tilted_moves_state* mv, void* stream);
+size_t sdeng_tilted_moves_workspace_bytes(const sdeng_tilted* desc);
+
 #ifdef __cplusplus
 }
 #endif

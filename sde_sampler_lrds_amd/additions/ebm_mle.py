@@ -2,7 +2,8 @@
 Monte Carlo), ``make_re_pairings`` (:198-216), ``re_step`` (:219-266) and ``re_sampler`` (:269-400, replica exchange), on top
 of the local moves of ``additions/mcmc.py``.  They are host compositions: what costs time is ``log_prob_and_grads(t, x)`` at
 every proposal, which ``hip_tempered_log_prob_and_grads`` serves from the HIP distribution kernels and ``ebm_log_prob_and_grads``,
-for an energy-based reference, from ``sdeng_tilted_eval`` (no autograd either way).  ``MaximumLikelihoodEBM`` (:401-808) is the
+for an energy-based reference, from ``sdeng_tilted_eval`` (no autograd either way); over either, the unpreconditioned local moves of a
+level run in one launch (``_native_route``).  ``MaximumLikelihoodEBM`` (:401-808) is the
 trainer around them: its energies and their parameter gradients come from ``sdeng_tilted_vjp``, one launch per ``net.energy`` call.
 
 Same arguments, return values, random-number consumption order and diagnostics as the reference, including the
@@ -28,30 +29,59 @@ def hip_tempered_log_prob_and_grads(target, prior):
     return fn
 
 
-# Local moves of a level as ONE HIP launch (csrc/prep_kernels.hip k_chain_moves) when the annealing path is
-# hip_tempered_log_prob_and_grads and the moves are not preconditioned.  NATIVE_NOISE = False: the random numbers still come from torch's
-# generator, drawn in the reference's order (the chains are then the reference's chains, tests/golden/smc_*.npz, re_*.npz);
-# True: counter-based draws inside the kernel (seeded by NATIVE_SEED and a per-call counter).
+# Local moves of a level as ONE HIP launch when they are not preconditioned and the density is one the engine knows as a whole: the
+# annealing path of hip_tempered_log_prob_and_grads (csrc/prep_kernels.hip k_chain_moves, sdeng_langevin_moves) or an energy-based
+# reference -- ebm_log_prob_and_grads(net) or the trainer's own MaximumLikelihoodEBM.log_prob_and_grads -- (csrc/tilted_moves_inst.hip
+# k_tilted_moves, sdeng_tilted_moves).  NATIVE_MOVES = False: the host loop, one evaluation launch per move.  NATIVE_NOISE = False: the
+# random numbers still come from torch's generator, drawn in the reference's order (the chains are then the reference's chains,
+# tests/golden/smc_*.npz, re_*.npz); True: counter-based draws inside the kernel (seeded by NATIVE_SEED and a per-call counter).
 NATIVE_MOVES, NATIVE_NOISE, NATIVE_SEED = True, False, 1
 _native_calls = [0]
 
 
-def _native_pair(log_prob_and_grads, x, precond):
-    pair = getattr(log_prob_and_grads, "hip_pair", None)
-    if not NATIVE_MOVES or pair is None or precond is not None or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32:
+class _EbmRoute:
+    """The route of local moves over an energy-based reference: its net."""
+
+    def __init__(self, net):
+        self.net = net
+
+
+def _hip_net(log_prob_and_grads):
+    """The energy-based reference behind a ``log_prob_and_grads`` callable, or None: the mark of ``ebm_log_prob_and_grads``, or the
+    trainer's bound method (``MaximumLikelihoodEBM.hip_net``)."""
+    net = getattr(log_prob_and_grads, "hip_net", None)
+    if net is None and getattr(log_prob_and_grads, "__func__", None) is MaximumLikelihoodEBM.log_prob_and_grads:
+        net = log_prob_and_grads.__self__.hip_net
+    return net
+
+
+def _native_route(log_prob_and_grads, x, precond):
+    """The one route decision of the samplers' local moves: the (target, prior) pair of an analytic annealing path, an ``_EbmRoute``,
+    or None -- the host loop.  No condition on the size: the one-launch moves were no slower at any measured shape (profiles/tilted_moves.log)."""
+    if not NATIVE_MOVES or precond is not None or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32:
         return None
-    return pair
+    pair = getattr(log_prob_and_grads, "hip_pair", None)
+    if pair is not None:
+        return pair
+    net = _hip_net(log_prob_and_grads)
+    if net is not None and E.tilted_refusal(net, x.device) is None:  # "tilted_eval would accept this net"; else the host loop raises its error
+        return _EbmRoute(net)
+    return None
 
 
-def _native_run(pair, t, x, lp, grad, step, n_moves, keep_from, use_ula, target_acceptance, want_samples=True):
-    """n_moves local moves of all chains; x / lp / grad / step ([B,d], [B], [B,d], [B] contiguous) are updated in place.  ``grad is None``:
-    random-walk Metropolis moves on ``pair[0]`` alone (no ``t``, no ULA); otherwise Langevin moves on the path between the pair."""
+def _native_run(route, t, x, lp, grad, step, n_moves, keep_from, use_ula, target_acceptance, want_samples=True):
+    """n_moves local moves of all chains; x / lp / grad / step ([B,d], [B], [B,d], [B] contiguous) are updated in place.  ``route``: what
+    ``_native_route`` returned.  A pair with ``grad is None``: random-walk Metropolis moves on ``pair[0]`` alone (no ``t``, no ULA);
+    otherwise Langevin moves on the path between the pair, or over the energy-based reference at the rows' times ``t``."""
     _native_calls[0] += 1
     kw = dict(keep_from=keep_from, target_acceptance=target_acceptance if not use_ula else 0.0, noise="philox" if NATIVE_NOISE else "torch",
               seed=(NATIVE_SEED + 0x9E3779B97F4A7C15 * _native_calls[0]) & 0xFFFFFFFFFFFFFFFF, want_samples=want_samples)
+    if isinstance(route, _EbmRoute):
+        with torch.no_grad():
+            return E.tilted_moves(route.net, t, x, lp, grad, step, n_moves, unadjusted=use_ula, **kw)
     if grad is None:
-        return E.rwmh_moves(pair[0], x, lp, step, n_moves, **kw)
-    return E.langevin_moves(pair[0], pair[1], x, lp, grad, step, n_moves, t=t, unadjusted=use_ula, **kw)
+        return E.rwmh_moves(route[0], x, lp, step, n_moves, **kw)
+    return E.langevin_moves(route[0], route[1], x, lp, grad, step, n_moves, t=None if t is None else t.reshape(-1), unadjusted=use_ula, **kw)
 
 
 def _pmul(mat, v):
@@ -136,11 +166,11 @@ def smc_sampler(x_init, times, log_prob_and_grads, n_warmup_mcmc_steps, n_mcmc_s
                 if use_precond:
                     pgrad = pgrad[idx]
                 log_w.zero_()
-        pair = _native_pair(log_prob_and_grads, x, precond)
-        if pair is not None:  # all warm-up and sampling moves of the level in one launch
+        route = _native_route(log_prob_and_grads, x, precond)
+        if route is not None:  # all warm-up and sampling moves of the level in one launch
             x, lp, grad = x.contiguous(), lp.contiguous().clone(), grad.contiguous().clone()
             step_flat = step.to(torch.float32).reshape(-1).expand(B).contiguous().clone()
-            got, acc_sum, _ = _native_run(pair, times[lvl].reshape(-1), x, lp, grad, step_flat, n_warmup_mcmc_steps + n_mcmc_steps,
+            got, acc_sum, _ = _native_run(route, times[lvl], x, lp, grad, step_flat, n_warmup_mcmc_steps + n_mcmc_steps,
                                           n_warmup_mcmc_steps, use_ula, target_acceptance)
             samples[lvl] = got
             step = step_flat.view(step.shape)
@@ -226,7 +256,7 @@ def re_sampler(x_init, times, log_prob_and_grads, swap_frequency, n_warmup_mcmc_
     lp, grad = move.f(x)
     pgrad = move.pgrad(grad)
     pairs = make_re_pairings(n_levels, x_init.device)
-    native = _native_pair(log_prob_and_grads, x, precond)
+    native = _native_route(log_prob_and_grads, x, precond)
     total = n_warmup_mcmc_steps + n_mcmc_steps
     if native is not None:
         x, lp, grad = x.contiguous().clone(), lp.contiguous().clone(), grad.contiguous().clone()
@@ -257,7 +287,7 @@ def re_sampler(x_init, times, log_prob_and_grads, swap_frequency, n_warmup_mcmc_
         else:  # the local moves up to the next swap step in one launch
             run = min(swap_frequency - it % swap_frequency, total - it)
             keep = max(0, n_warmup_mcmc_steps - it)
-            got, _, last = _native_run(native, t_flat.reshape(-1), x, lp, grad, step, run, min(keep, run), use_ula, target_acceptance, want_samples=keep < run)
+            got, _, last = _native_run(native, t_flat, x, lp, grad, step, run, min(keep, run), use_ula, target_acceptance, want_samples=keep < run)
             if keep < run:
                 first = it + keep - n_warmup_mcmc_steps
                 samples[:, first:first + run - keep] = got.view(run - keep, n_levels, B, *data_shape).transpose(0, 1)
@@ -275,14 +305,16 @@ def re_sampler(x_init, times, log_prob_and_grads, swap_frequency, n_warmup_mcmc_
 def ebm_log_prob_and_grads(net):
     """The ``log_prob_and_grads(t, x)`` callable ``smc_sampler`` / ``re_sampler`` take, for an energy-based reference ``net``
     (``GMMTitledPotential`` / ``GaussTiltedPotential``): mirror of ``MaximumLikelihoodEBM.log_prob_and_grads``
-    (additions/ebm_mle.py:440-446), served by one ``sdeng_tilted_eval`` launch per call -- no autograd.  The samplers' host loops call it
-    once per move."""
+    (additions/ebm_mle.py:440-446), served by one ``sdeng_tilted_eval`` launch per call -- no autograd.  The samplers call it for the
+    initial evaluation and the swap steps; their local moves run over ``net`` in one launch per level (``sdeng_tilted_moves``) unless
+    ``NATIVE_MOVES`` is off or the moves are preconditioned -- then the host loops call it once per move."""
     if not getattr(net, "has_unnorm_log_prob_and_grad", False):
         raise E.UnsupportedByEngine("ebm_log_prob_and_grads: the net has no unnorm_log_prob_and_grad (autograd energies are not on the HIP path)")
 
     def fn(t, x):
         with torch.no_grad():
             return E.tilted_eval(net, t, x.detach())
+    fn.hip_net = net  # lets the samplers above run whole levels of local moves in one launch (sdeng_tilted_moves)
     return fn
 
 
@@ -319,6 +351,12 @@ class MaximumLikelihoodEBM(torch.nn.Module):
         kw = dict(sde=self.sde) if self.use_snr_adapted_disc else {}
         self.register_buffer("times", get_timesteps(start=self.start_eps, end=self.sde.terminal_t - self.end_eps, steps=self.n_steps,
                                                     **kw).unsqueeze(-1))
+
+    @property
+    def hip_net(self):
+        """The net when ``log_prob_and_grads`` is its ``unnorm_log_prob_and_grad`` and nothing else: what the samplers' route decision
+        reads off the bound method."""
+        return self.net if getattr(self.net, "has_unnorm_log_prob_and_grad", False) else None
 
     def log_prob_and_grads(self, t, y):
         if self.net.has_unnorm_log_prob_and_grad:
@@ -367,6 +405,16 @@ class MaximumLikelihoodEBM(torch.nn.Module):
         precond = (self.precond_matrix_per_noise, self.precond_matrix_chol_per_noise) if self.use_precond else None
         move = _LocalMove(f, self.use_ula, self.target_acceptance, precond)
         pgrad, acc = move.pgrad(grad), None
+        total = n_warmup_mcmc_steps + n_mcmc_steps
+        with torch.no_grad():  # (as f evaluates: train calls this in grad mode with trainable parameters)
+            route = _native_route(self.log_prob_and_grads, x, precond) if total > 0 and torch.is_tensor(self.step_sizes_per_noise) else None
+        if route is not None:  # all moves of the batch in one launch
+            lp, grad = lp.contiguous().clone(), grad.contiguous().clone()
+            steps = self.step_sizes_per_noise
+            step = steps.to(torch.float32).reshape(-1).expand(x.shape[0]).contiguous().clone()
+            xs_neg, _, last = _native_run(route, t_rows, x, lp, grad, step, total, n_warmup_mcmc_steps, self.use_ula, self.target_acceptance)
+            self.step_sizes_per_noise = step.view(steps.shape)
+            return xs_neg, ({} if self.use_ula else {"local_acc": last.mean().cpu()})
         for it in range(n_warmup_mcmc_steps + n_mcmc_steps):
             x, lp, grad, pgrad, self.step_sizes_per_noise, log_acc = move(x, lp, grad, pgrad, self.step_sizes_per_noise)
             if log_acc is not None:

@@ -1180,8 +1180,9 @@ static TiltedLayout tilted_layout(const sdeng_tilted* t, bool train = false) {
   L.total = o;
   return L;
 }
-// `who`: the entry point, for the messages; `train`: sdeng_tilted_vjp, where log_prob and grad may both be absent
-static int check_tilted(const sdeng_tilted* t, const char* who = "tilted_eval", bool train = false) {
+// `who`: the entry point, for the messages; `train`: sdeng_tilted_vjp, where log_prob and grad may both be absent; `moves`:
+// sdeng_tilted_moves, which ignores x, log_prob and grad (the chain state is in its own argument block)
+static int check_tilted(const sdeng_tilted* t, const char* who = "tilted_eval", bool train = false, bool moves = false) {
   if (!t) return fail(SDENG_E_INVALID, "%s: null descriptor", who);
   if (t->abi_version != SDENG_ABI_VERSION) return fail(SDENG_E_INVALID, "ABI version %d, library has %d", t->abi_version, SDENG_ABI_VERSION);
   if (t->d < 1 || t->d > 128) return fail(SDENG_E_INVALID, "%s: d = %d outside [1, 128]", who, t->d);
@@ -1194,18 +1195,51 @@ static int check_tilted(const sdeng_tilted* t, const char* who = "tilted_eval", 
                 t->num_layers, t->channels);
   if (t->tilt_type != SDENG_TILT_DOT) return fail(SDENG_E_UNSUPPORTED, "%s: tilt_type 'dot' only (type %d given)", who, t->tilt_type);
   if (t->use_scaling_factor) return fail(SDENG_E_UNSUPPORTED, "%s: use_scaling_factor (the DRL scaling argument) is not supported", who);
-  const void* need[] = {t->x, t->tinfo, t->w_in, t->b_in, t->w_out, t->b_out, t->te_coeff, t->te_phase, t->te_w1, t->te_b1, t->te_w2, t->te_b2,
+  const void* need[] = {moves ? t->tinfo : t->x, t->tinfo, t->w_in, t->b_in, t->w_out, t->b_out, t->te_coeff, t->te_phase, t->te_w1, t->te_b1, t->te_w2, t->te_b2,
                         t->mean_gauss, t->var_gauss, t->weights, t->means, t->vars, t->w_h[0], t->w_h[1], t->w_h[2], t->w_h[3],
                         t->b_h[0], t->b_h[1], t->b_h[2], t->b_h[3]};
   for (const void* p : need)
     if (!p) return fail(SDENG_E_INVALID, "%s: null pointer in the descriptor", who);
   if (t->full_cov && !t->eigvecs) return fail(SDENG_E_INVALID, "%s: full_cov without eigvecs", who);
-  if (!train && !t->log_prob && !t->grad) return fail(SDENG_E_INVALID, "%s: nothing to compute (log_prob and grad are both NULL)", who);
+  if (!train && !moves && !t->log_prob && !t->grad) return fail(SDENG_E_INVALID, "%s: nothing to compute (log_prob and grad are both NULL)", who);
   return 0;
 }
 extern "C" size_t sdeng_tilted_eval_workspace_bytes(const sdeng_tilted* t) {
   if (check_tilted(t)) return 0;
   return tilted_layout(t).total * sizeof(float);
+}
+// the packed images and constants of the net and the prior, at the head of the workspace of every tilted entry point
+static int pack_tilted(const sdeng_tilted* t, const TiltedLayout& L, float* ws, hipStream_t s) {
+  const int d = t->d, H = TL_H;
+  TiltedPackArgs p;
+  memset(&p, 0, sizeof(p));
+  p.pack = ws + L.pack; p.consts = ws + L.consts;
+  p.coeff = t->te_coeff; p.phase = t->te_phase; p.mean_gauss = t->mean_gauss; p.var_gauss = t->var_gauss;
+  p.weights = t->weights; p.means = t->means; p.vars = t->vars; p.d = d; p.K = t->k;
+  int n = 0;
+  auto job = [&](int slot, const float* W, int n_out, int n_in, int ld, int col0, int transpose, int scale_n, const float* bias, int bias_off) {
+    TiltedPackJob& j = p.job[n++];
+    j.src = W; j.scale_src = W; j.bias = bias; j.n_out = n_out; j.n_in = n_in; j.ld = ld; j.col0 = col0; j.transpose = transpose;
+    j.scale_n = scale_n; j.slot = slot; j.bias_off = bias ? bias_off : -1;
+  };
+  job(TL_TE1S, t->te_w1, H, H, 2 * H, 0, 0, 2 * H * H, t->te_b1, TL_C_BTE1);  // the sine and cosine halves share the matrix's scale
+  job(TL_TE1C, t->te_w1, H, H, 2 * H, H, 0, 2 * H * H, nullptr, 0);
+  job(TL_TE2, t->te_w2, H, H, H, 0, 0, H * H, t->te_b2, TL_C_BTE2);
+  job(TL_WIN, t->w_in, H, d, d, 0, 0, H * d, t->b_in, TL_C_BIN);
+  for (int l = 0; l < 4; ++l) job(TL_WH + l, t->w_h[l], H, H, H, 0, 0, H * H, t->b_h[l], TL_C_BH + 128 * l);
+  job(TL_WOUT, t->w_out, d, H, H, 0, 0, d * H, t->b_out, TL_C_BOUT);
+  job(TL_WOUT_T, t->w_out, H, d, H, 0, 1, d * H, nullptr, 0);  // W_out^T: [128 x d]
+  for (int l = 0; l < 4; ++l) job(TL_WH_T + l, t->w_h[l], H, H, H, 0, 1, H * H, nullptr, 0);
+  job(TL_WIN_T, t->w_in, d, H, d, 0, 1, H * d, nullptr, 0);    // W_in^T: [d x 128]
+  if (t->full_cov)
+    for (int k = 0; k < t->k; ++k) {
+      const float* P = t->eigvecs + static_cast<size_t>(k) * d * d;
+      job(TL_EIG + 2 * k, P, d, d, d, 0, 1, d * d, nullptr, 0);      // y = P^T z
+      job(TL_EIG + 2 * k + 1, P, d, d, d, 0, 0, d * d, nullptr, 0);  // P q
+    }
+  p.njobs = n;
+  SD_HIP(sd_launch_tilted_pack(p, s));
+  return 0;
 }
 // the pack (unless reused) and the one launch of either entry point; `rows`: the training instantiation
 static int run_tilted(const sdeng_tilted* t, const TiltedRows* rows, void* stream) {
@@ -1214,37 +1248,8 @@ static int run_tilted(const sdeng_tilted* t, const TiltedRows* rows, void* strea
   const size_t need = L.total * sizeof(float);
   if (!t->workspace || t->workspace_bytes < need) return fail(SDENG_E_WORKSPACE, "workspace %zu bytes, need %zu", t->workspace_bytes, need);
   float* ws = static_cast<float*>(t->workspace);
-  const int d = t->d, H = TL_H;
-  if (!(t->flags & SDENG_FLAG_REUSE_PACK)) {
-    TiltedPackArgs p;
-    memset(&p, 0, sizeof(p));
-    p.pack = ws + L.pack; p.consts = ws + L.consts;
-    p.coeff = t->te_coeff; p.phase = t->te_phase; p.mean_gauss = t->mean_gauss; p.var_gauss = t->var_gauss;
-    p.weights = t->weights; p.means = t->means; p.vars = t->vars; p.d = d; p.K = t->k;
-    int n = 0;
-    auto job = [&](int slot, const float* W, int n_out, int n_in, int ld, int col0, int transpose, int scale_n, const float* bias, int bias_off) {
-      TiltedPackJob& j = p.job[n++];
-      j.src = W; j.scale_src = W; j.bias = bias; j.n_out = n_out; j.n_in = n_in; j.ld = ld; j.col0 = col0; j.transpose = transpose;
-      j.scale_n = scale_n; j.slot = slot; j.bias_off = bias ? bias_off : -1;
-    };
-    job(TL_TE1S, t->te_w1, H, H, 2 * H, 0, 0, 2 * H * H, t->te_b1, TL_C_BTE1);  // the sine and cosine halves share the matrix's scale
-    job(TL_TE1C, t->te_w1, H, H, 2 * H, H, 0, 2 * H * H, nullptr, 0);
-    job(TL_TE2, t->te_w2, H, H, H, 0, 0, H * H, t->te_b2, TL_C_BTE2);
-    job(TL_WIN, t->w_in, H, d, d, 0, 0, H * d, t->b_in, TL_C_BIN);
-    for (int l = 0; l < 4; ++l) job(TL_WH + l, t->w_h[l], H, H, H, 0, 0, H * H, t->b_h[l], TL_C_BH + 128 * l);
-    job(TL_WOUT, t->w_out, d, H, H, 0, 0, d * H, t->b_out, TL_C_BOUT);
-    job(TL_WOUT_T, t->w_out, H, d, H, 0, 1, d * H, nullptr, 0);  // W_out^T: [128 x d]
-    for (int l = 0; l < 4; ++l) job(TL_WH_T + l, t->w_h[l], H, H, H, 0, 1, H * H, nullptr, 0);
-    job(TL_WIN_T, t->w_in, d, H, d, 0, 1, H * d, nullptr, 0);    // W_in^T: [d x 128]
-    if (t->full_cov)
-      for (int k = 0; k < t->k; ++k) {
-        const float* P = t->eigvecs + static_cast<size_t>(k) * d * d;
-        job(TL_EIG + 2 * k, P, d, d, d, 0, 1, d * d, nullptr, 0);      // y = P^T z
-        job(TL_EIG + 2 * k + 1, P, d, d, d, 0, 0, d * d, nullptr, 0);  // P q
-      }
-    p.njobs = n;
-    SD_HIP(sd_launch_tilted_pack(p, s));
-  }
+  const int d = t->d;
+  if (!(t->flags & SDENG_FLAG_REUSE_PACK)) SD_TRY(pack_tilted(t, L, ws, s));
   TiltedArgs a;
   memset(&a, 0, sizeof(a));
   a.M = t->M; a.B = t->rows_per_time; a.d = d; a.N = t->n_times; a.K = t->k; a.full = t->full_cov ? 1 : 0;
@@ -1280,4 +1285,64 @@ extern "C" int sdeng_tilted_vjp(const sdeng_tilted* t, const sdeng_tilted_rows* 
   for (int l = 0; l < 5; ++l) { rows.a[l] = r->a[l]; rows.d[l] = r->d[l]; }
   rows.xs = r->xs; rows.dv = r->dv;
   return run_tilted(t, &rows, stream);
+}
+
+// ---- Langevin moves over an energy-based reference: tilted_moves_inst.hip ------------------------------------------------------------
+// workspace: the layout of an evaluation with grad (so the packed images are where sdeng_tilted_eval keeps them), the per-wave slots one
+// layer longer (the time embedding's accumulator), then the proposal and proposal-gradient rows
+struct TiltedMovesLayout {
+  TiltedLayout L;
+  size_t prop, gprop, total;  // floats
+};
+static TiltedMovesLayout tilted_moves_layout(const sdeng_tilted* t) {
+  TiltedMovesLayout ml;
+  ml.L = tilted_layout(t, true);
+  size_t o = ml.L.hbuf + static_cast<size_t>(ml.L.grid) * ml.L.waves * TLM_HBUF_FLOATS;
+  const size_t rows = align64(static_cast<size_t>(t->M) * t->d);
+  ml.prop = o; o += rows;
+  ml.gprop = o; o += rows;
+  ml.total = o;
+  return ml;
+}
+static int check_tilted_moves(const sdeng_tilted* t, const sdeng_tilted_moves_state* mv) {
+  const char* who = "tilted_moves";
+  SD_TRY(check_tilted(t, who, false, true));
+  if (!mv) return fail(SDENG_E_INVALID, "%s: null move state", who);
+  if (!mv->x || !mv->lp || !mv->grad || !mv->step) return fail(SDENG_E_INVALID, "%s: x, lp, grad and step are all required", who);
+  if (mv->n_moves < 0) return fail(SDENG_E_INVALID, "%s: n_moves = %d < 0", who, mv->n_moves);
+  if (mv->keep_from < 0 || mv->keep_from > mv->n_moves)
+    return fail(SDENG_E_INVALID, "%s: keep_from = %d outside [0, n_moves = %d]", who, mv->keep_from, mv->n_moves);
+  if ((mv->z == nullptr) != (mv->u == nullptr) && !mv->unadjusted)  // (unadjusted moves read no uniforms)
+    return fail(SDENG_E_INVALID, "%s: inject both the normals and the uniforms, or neither (unadjusted moves: the normals alone)", who);
+  return 0;
+}
+extern "C" size_t sdeng_tilted_moves_workspace_bytes(const sdeng_tilted* t) {
+  if (check_tilted(t, "tilted_moves", false, true)) return 0;
+  return tilted_moves_layout(t).total * sizeof(float);
+}
+extern "C" int sdeng_tilted_moves(const sdeng_tilted* t, const sdeng_tilted_moves_state* mv, void* stream) {
+  SD_TRY(check_tilted_moves(t, mv));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const TiltedMovesLayout ml = tilted_moves_layout(t);
+  const TiltedLayout& L = ml.L;
+  const size_t need = ml.total * sizeof(float);
+  if (!t->workspace || t->workspace_bytes < need)
+    return fail(SDENG_E_WORKSPACE, "tilted_moves: workspace %zu bytes, need %zu", t->workspace_bytes, need);
+  if (mv->n_moves == 0) return 0;
+  float* ws = static_cast<float*>(t->workspace);
+  if (!(t->flags & SDENG_FLAG_REUSE_PACK)) SD_TRY(pack_tilted(t, L, ws, s));
+  TiltedArgs a;
+  memset(&a, 0, sizeof(a));
+  a.M = t->M; a.B = t->rows_per_time; a.d = t->d; a.N = t->n_times; a.K = t->k; a.full = t->full_cov ? 1 : 0;
+  a.use_st = t->use_s_t_scaling ? 1 : 0; a.ntiles = L.ntiles;
+  a.tinfo = t->tinfo; a.pack = ws + L.pack; a.consts = ws + L.consts; a.hbuf = ws + L.hbuf; a.trash = ws + L.trash;
+  TiltedMovesArgs m;
+  memset(&m, 0, sizeof(m));
+  m.x = mv->x; m.grad = mv->grad; m.lp = mv->lp; m.step = mv->step; m.prop = ws + ml.prop; m.gprop = ws + ml.gprop;
+  m.z = mv->z; m.u = mv->unadjusted ? nullptr : mv->u; m.samples = mv->samples; m.acc_sum = mv->acc_sum; m.acc_last = mv->acc_last;
+  m.K = mv->n_moves; m.keep_from = mv->keep_from; m.ula = mv->unadjusted ? 1 : 0; m.target_acc = mv->target_acceptance;
+  const Seed sd = split_seed(mv->seed);
+  m.seed_lo = sd.lo; m.seed_hi = sd.hi; m.chain0 = mv->chain0;
+  SD_HIP(sd_launch_tilted_moves(a, m, tiles_exact(t->d), L.grid, L.waves, s));
+  return 0;
 }

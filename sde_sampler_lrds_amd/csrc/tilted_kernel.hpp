@@ -72,7 +72,24 @@ struct TiltedPackArgs {
   int d, K, njobs;
   TiltedPackJob job[TL_NIMG];
 };
+// Langevin moves over the tilted density (k_tilted_moves, tilted_moves_inst.hip): the chain state next to the TiltedArgs of the net.
+// The caller's x / grad hold the current state and are updated in place on acceptance; prop / gprop are the proposal and the score at it.
+#define TLM_HBUF_FLOATS (6 * TL_HT * 64 * 4)  // per-wave slot: the five pre-activations and, as layer 5, the time embedding's accumulator: 48 KiB
+struct TiltedMovesArgs {
+  float *x, *grad;      // [M, d]
+  float *lp, *step;     // [M]
+  float *prop, *gprop;  // [M, d] workspace
+  const float* z;       // [K, M, d] or nullptr: Philox stream 8
+  const float* u;       // [K, M] or nullptr: Philox stream 9
+  float* samples;       // [K - keep_from, M, d] or nullptr
+  float *acc_sum, *acc_last;  // [M] or nullptr
+  int K, keep_from, ula;
+  float target_acc;
+  uint32_t seed_lo, seed_hi;
+  long long chain0;
+};
 int sd_launch_tilted_pack(const TiltedPackArgs& a, hipStream_t s);
+int sd_launch_tilted_moves(const TiltedArgs& a, const TiltedMovesArgs& mv, int NT, int grid, int waves, hipStream_t s);
 int sd_launch_tilted(const TiltedArgs& a, int NT, int grid, int waves, hipStream_t s);
 int sd_launch_tilted_train(const TiltedArgs& a, const TiltedRows& rows, int NT, int grid, int waves, hipStream_t s);
 inline int sd_tilted_waves(int ntiles) {  // waves per workgroup: as many as still leave a workgroup for every CU

@@ -698,10 +698,9 @@ def mmd_median(X: torch.Tensor, Y: torch.Tensor):
     return out[0], out[1]
 
 
-def _chain_moves(who, target, prior, x, lp, grad, step, n_moves, t, keep_from, unadjusted, target_acceptance, noise, seed, chain0, want_samples):
-    """The launcher behind langevin_moves and rwmh_moves (``who``; random-walk Metropolis has no prior / grad / t / unadjusted).  Everything
-    the kernel indexes is checked here, before anything is built or launched."""
-    langevin = who == "langevin_moves"
+def _check_chain_state(who, x, lp, grad, step, n_moves, keep_from, noise, t=None):
+    """What every one-launch move kernel indexes (langevin_moves, rwmh_moves, tilted_moves), checked before anything is built or launched.
+    ``grad is None``: a move without gradients.  Returns (B, d, n_moves, keep_from)."""
     require_gpu(x)
     if x.dim() != 2:
         raise ValueError(f"{who}: x must be [B, d], got {tuple(x.shape)}")
@@ -709,40 +708,68 @@ def _chain_moves(who, target, prior, x, lp, grad, step, n_moves, t, keep_from, u
     n_moves, keep_from = int(n_moves), int(keep_from)
     if lp.numel() != B or step.numel() != B:
         raise ValueError(f"{who}: lp and step must hold one value per chain (B = {B}), got {lp.numel()} and {step.numel()}")
-    if langevin and grad.shape != x.shape:
+    if grad is not None and grad.shape != x.shape:
         raise ValueError(f"{who}: grad must have the shape of x {tuple(x.shape)}, got {tuple(grad.shape)}")
     if t is not None and t.numel() not in (1, B):
         raise ValueError(f"{who}: t must hold one tempering weight, or one per chain (B = {B}), got {t.numel()}")
     if not 0 <= keep_from <= n_moves:
         raise ValueError(f"{who}: 0 <= keep_from <= n_moves, got keep_from = {keep_from}, n_moves = {n_moves}")
-    if noise not in ("torch", "philox"):
-        raise ValueError("noise: 'torch' or 'philox'")
-    state = (("x", x), ("lp", lp), ("step", step)) + ((("grad", grad),) if langevin else ())
+    injected = isinstance(noise, tuple) and len(noise) == 2 and torch.is_tensor(noise[0])
+    if not injected and noise not in ("torch", "philox"):
+        raise ValueError("noise: 'torch', 'philox' or the pair (z [n_moves, B, d], u [n_moves, B] or None)")
+    state = (("x", x), ("lp", lp), ("step", step)) + ((("grad", grad),) if grad is not None else ())
+    if injected:
+        if tuple(noise[0].shape) != (n_moves, B, d) or (noise[1] is not None and tuple(noise[1].shape) != (n_moves, B)):
+            raise ValueError(f"{who}: injected noise must be z [{n_moves}, {B}, {d}] and u [{n_moves}, {B}]")
+        state += (("z", noise[0]),) + ((("u", noise[1]),) if noise[1] is not None else ())
     for ok in (lambda v: v.dtype == torch.float32 and v.is_contiguous(), lambda v: v.is_cuda):
         for name, v in state:
             if not ok(v):
-                raise ValueError(f"{who}: {name} must be a contiguous float32 CUDA tensor (it is updated in place)")
+                raise ValueError(f"{who}: {name} must be a contiguous float32 CUDA tensor (the kernel reads and writes it in place)")
+    return B, d, n_moves, keep_from
+
+
+def _move_buffers(noise, n_moves, keep_from, B, d, unadjusted, want_samples, device):
+    """(z, u, samples, acc_sum, acc_last) of a one-launch move kernel.  ``noise='torch'``: the reference's consumption order, one randn
+    per proposal, then one rand per accept test; a (z, u) pair: the caller's own draws; otherwise z = u = None (Philox in the kernel)."""
+    z = u = None
+    if isinstance(noise, tuple):
+        z, u = noise[0], (noise[1] if not unadjusted else None)
+        if u is None and not unadjusted:
+            raise ValueError("injected noise: an adjusted move needs the uniforms u as well")
+    elif noise == "torch":
+        z = torch.empty(n_moves, B, d, dtype=torch.float32, device=device)
+        u = torch.empty(n_moves, B, dtype=torch.float32, device=device) if not unadjusted else None
+        for m in range(n_moves):
+            z[m] = torch.randn((B, d), device=device)
+            if u is not None:
+                u[m] = torch.rand((B,), device=device)
+    samples = torch.empty(n_moves - keep_from, B, d, dtype=torch.float32, device=device) if want_samples else None
+    acc = torch.zeros(B, dtype=torch.float32, device=device) if not unadjusted else None
+    last = torch.ones(B, dtype=torch.float32, device=device) if not unadjusted else None
+    return z, u, samples, acc, last
+
+
+def _ptr(v):
+    return None if v is None else v.data_ptr()
+
+
+def _chain_moves(who, target, prior, x, lp, grad, step, n_moves, t, keep_from, unadjusted, target_acceptance, noise, seed, chain0, want_samples):
+    """The launcher behind langevin_moves and rwmh_moves (``who``; random-walk Metropolis has no prior / grad / t / unadjusted).  Everything
+    the kernel indexes is checked here, before anything is built or launched."""
+    langevin = who == "langevin_moves"
+    B, d, n_moves, keep_from = _check_chain_state(who, x, lp, grad if langevin else None, step, n_moves, keep_from, noise, t)
     if langevin and "Checkerboard" in (_name(target), _name(prior)):
         raise UnsupportedByEngine(f"{who}: no moves on a checkerboard (log-density -inf on a set of positive mass; zero score)")
     lib = L.lib()
     device, keep = x.device, []
     dt = C.byref(dist_desc(target, device, keep))
     dp = C.byref(dist_desc(prior, device, keep)) if prior is not None else None
-    z = u = None
-    if noise == "torch":
-        z = torch.empty(n_moves, B, d, dtype=torch.float32, device=device)
-        u = torch.empty(n_moves, B, dtype=torch.float32, device=device) if not unadjusted else None
-        for m in range(n_moves):  # the reference's consumption order: one randn per proposal, then one rand per accept test
-            z[m] = torch.randn((B, d), device=device)
-            if u is not None:
-                u[m] = torch.rand((B,), device=device)
+    z, u, samples, acc, last = _move_buffers(noise, n_moves, keep_from, B, d, unadjusted, want_samples, device)
     tt = None if t is None else t.detach().to(device=device, dtype=torch.float32).reshape(-1).expand(B).contiguous()
-    samples = torch.empty(n_moves - keep_from, B, d, dtype=torch.float32, device=device) if want_samples else None
-    acc = torch.zeros(B, dtype=torch.float32, device=device) if not unadjusted else None
-    last = torch.ones(B, dtype=torch.float32, device=device) if not unadjusted else None
     need = lib.sdeng_rwmh_moves_workspace_bytes(dt, d) if not langevin else lib.sdeng_langevin_moves_workspace_bytes(dp, dt, d)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
-    ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+    ptr = _ptr
     tail = (ptr(z), ptr(u), int(seed), int(chain0), ptr(samples), ptr(acc), ptr(last), ws.data_ptr(), ws.numel(), _stream_ptr(device))
     if not langevin:
         L.check(lib.sdeng_rwmh_moves(dt, B, d, n_moves, keep_from, float(target_acceptance), ptr(x), ptr(lp), ptr(step), *tail))
@@ -1110,17 +1137,10 @@ def tilted_eval(net, t, x: torch.Tensor, want_grad=True, want_logp=True, per_row
     return _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, False)[:2]
 
 
-def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
-    """The one launch behind tilted_eval (sdeng_tilted_eval) and tilted_vjp (``train``: sdeng_tilted_vjp, with the per-row arrays)."""
-    require_gpu(x)
-    lib = L.lib()
-    device, keep = x.device, []
-    xin = _f32c(x)
-    if xin.dim() != 2:
-        raise ValueError("tilted_eval: x must be [M, d]")
-    M, dim = xin.shape
+def _tilted_rows_desc(net, t, M, dim, device, keep, per_row_times=False):
+    """sdeng_tilted of ``net`` over M rows at the times ``t``, without its state, outputs and workspace; and (n_times, B, time table on the
+    device).  The time table of a tensor the samplers pass again and again is made once (reading a device tensor back waits for the stream)."""
     t = torch.as_tensor(t)
-    # the time table of a tensor the samplers pass again and again is made once (reading a device tensor back waits for the stream)
     def table(tt, per_row=False):
         n, b, info = tilted_times(net, tt, M, per_row)
         return n, b, info.to(device)
@@ -1131,7 +1151,34 @@ def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
         raise ValueError(f"tilted_eval: x has {dim} features, the potential {d.d}")
     d.M, d.n_times, d.rows_per_time = M, n_times, B
     keep.append(tdev)
-    d.x, d.tinfo = xin.data_ptr(), tdev.data_ptr()
+    d.tinfo = tdev.data_ptr()
+    return d, (n_times, B, tdev)
+
+
+def _tilted_workspace(net, d, need, device):
+    """The workspace of a tilted launch into ``d``: the net's own, whose head holds the packed images (every tilted entry point keeps them
+    in the same place), re-made only when a parameter or buffer changed or the call needs more room."""
+    versions = _tilted_versions(net, device)
+    hit = _TILTED_PACKS.get(net)
+    if hit is not None and hit[0] == versions and hit[1].numel() >= need:
+        ws, d.flags = hit[1], L.FLAG_REUSE_PACK
+    else:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        _TILTED_PACKS[net] = (versions, ws)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+
+
+def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
+    """The one launch behind tilted_eval (sdeng_tilted_eval) and tilted_vjp (``train``: sdeng_tilted_vjp, with the per-row arrays)."""
+    require_gpu(x)
+    lib = L.lib()
+    device, keep = x.device, []
+    xin = _f32c(x)
+    if xin.dim() != 2:
+        raise ValueError("tilted_eval: x must be [M, d]")
+    M, dim = xin.shape
+    d, (n_times, B, tdev) = _tilted_rows_desc(net, t, M, dim, device, keep, per_row_times)
+    d.x = xin.data_ptr()
     logp = torch.empty(M, dtype=torch.float32, device=device) if want_logp else None
     grad = torch.empty(M, dim, dtype=torch.float32, device=device) if want_grad else None
     d.log_prob, d.grad = (logp.data_ptr() if want_logp else None), (grad.data_ptr() if want_grad else None)
@@ -1150,16 +1197,62 @@ def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
         need = lib.sdeng_tilted_eval_workspace_bytes(C.byref(d))
     if need == 0:
         _check_supported(launch())  # the descriptor is rejected: fetch the code and the reason
-    versions = _tilted_versions(net, device)
-    hit = _TILTED_PACKS.get(net)
-    if hit is not None and hit[0] == versions and hit[1].numel() >= need:
-        ws, d.flags = hit[1], L.FLAG_REUSE_PACK
-    else:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        _TILTED_PACKS[net] = (versions, ws)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    _tilted_workspace(net, d, need, device)
     _check_supported(launch())
     return logp, grad, arrays, (n_times, B, tdev[:, 0])
+
+
+def tilted_refusal(net, device):
+    """Why ``tilted_eval`` / ``tilted_moves`` would refuse ``net`` as it stands -- the reason, in words -- or None: the checks of the
+    descriptor compiler and of the library on the net, made without a launch.  The samplers' route decision asks this before it commits
+    a level to the one-launch path; a refused net stays on the host loop, whose first evaluation raises the error itself."""
+    if tilted_needs_param_grad(net):
+        return "trainable parameters in grad mode"
+    try:
+        d = tilted_desc(net, device, [])
+    except UnsupportedByEngine as e:
+        return str(e)
+    if (d.num_layers, d.channels) != (6, 128):
+        return f"FourierMLP(num_layers={d.num_layers}, channels={d.channels}): the kernel is built for 6 x 128"
+    if d.tilt_type != L.TILT_DOT:
+        return f"tilt_type {net.tilt_type!r}: the kernel has 'dot'"
+    if d.use_scaling_factor:
+        return "use_scaling_factor (DRL)"
+    if not 1 <= d.d <= 128 or not 1 <= d.k <= 16:
+        return f"d = {d.d}, k = {d.k} outside the kernel's range"
+    return None
+
+
+def tilted_moves(net, t, x, lp, grad, step, n_moves, *, keep_from=0, unadjusted=False, target_acceptance=0.0, noise="torch", seed=0, chain0=0,
+                 want_samples=True):
+    """sdeng_tilted_moves: ``n_moves`` MALA / ULA moves of all chains over the energy-based reference ``net`` in one launch
+    (include/sdeng.h) -- ``langevin_moves`` with the density of ``tilted_eval``.  ``t``: the chains' times, as ``tilted_eval`` takes them (a
+    scalar, or one per row; rows of unequal runs become one time per chain).  ``x`` [M,d], ``lp`` [M], ``grad`` [M,d] (``tilted_eval`` at
+    ``x``) and ``step`` [M] are updated IN PLACE.  ``noise='torch'``: per move ``randn((M, d))`` then ``rand((M,))`` from torch's generator,
+    the order additions/mcmc.py consumes them; ``noise='philox'``: drawn in the kernel (streams 8 / 9, keyed by ``seed`` and ``chain0`` + row);
+    a pair ``(z [n_moves, M, d], u [n_moves, M])``: the caller's own draws.  Refusals are ``tilted_eval``'s.
+    Returns (samples [n_moves - keep_from, M, d] or None, acc_sum [M] or None, acc_last [M] or None)."""
+    who = "tilted_moves"
+    M, dim, n_moves, keep_from = _check_chain_state(who, x, lp, grad, step, n_moves, keep_from, noise)
+    if tilted_needs_param_grad(net):
+        raise UnsupportedByEngine("tilted_moves computes no gradient with respect to the net's parameters: call it under torch.no_grad() "
+                                  "or with requires_grad_(False) parameters")
+    lib = L.lib()
+    device, keep = x.device, []
+    d, _ = _tilted_rows_desc(net, t, M, dim, device, keep)
+    z, u, samples, acc, last = _move_buffers(noise, n_moves, keep_from, M, dim, unadjusted, want_samples, device)
+    mv = L.TiltedMovesState()
+    mv.n_moves, mv.keep_from, mv.unadjusted, mv.target_acceptance = n_moves, keep_from, int(bool(unadjusted)), float(target_acceptance)
+    mv.x, mv.lp, mv.grad, mv.step = x.data_ptr(), lp.data_ptr(), grad.data_ptr(), step.data_ptr()
+    mv.z, mv.u, mv.seed, mv.chain0 = _ptr(z), _ptr(u), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain0)
+    mv.samples, mv.acc_sum, mv.acc_last = _ptr(samples), _ptr(acc), _ptr(last)
+    launch = lambda: lib.sdeng_tilted_moves(C.byref(d), C.byref(mv), _stream_ptr(device))  # noqa: E731
+    need = lib.sdeng_tilted_moves_workspace_bytes(C.byref(d))
+    if need == 0:
+        _check_supported(launch())  # the descriptor is rejected: fetch the code and the reason
+    _tilted_workspace(net, d, need, device)
+    _check_supported(launch())
+    return samples, acc, last
 
 
 def tilted_vjp(net, t, x: torch.Tensor, want_grad=False, per_row_times=False):
