@@ -8,6 +8,7 @@
 //   k_logz_*        elbo / logsumexp / variance / ESS / softmax weights          (losses/oc.py:150-161)
 //   k_philox        the step loop's counter-based normals, standalone            (tests)
 #include "sim_device.hpp"
+#include "langevin_rules.hpp"
 #include "prep_kernels.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -756,7 +757,8 @@ __global__ void __launch_bounds__(SD_EVAL_THREADS) k_dist_eval(DistEvalArgs a) {
 // Local moves of the annealed samplers and of the learned-reference data set: one thread per chain, the chain's rows in LDS,
 // all K moves of a level in ONE launch -- the reference (and the host composition this replaces) spends ~30 small launches per move.
 // One skeleton, two instantiations: Langevin (MALA / ULA, the runtime flag a.ula) and random-walk Metropolis, which has no gradient, no
-// score call and no prior.  What differs per move is marked `if constexpr`; everything else is written once.
+// score call and no prior.  What differs per move is marked `if constexpr`; everything else is written once.  The scalar rules (log
+// acceptance, accept test, step adaptation, acceptance probability) are langevin_rules.hpp's, shared with k_tilted_moves.
 // ------------------------------------------------------------------------------------------------
 // LDS rows per chain.  Langevin: x, grad, proposal, gradient at the proposal, scratch score row.  RWMH: x, proposal.
 constexpr int sd_move_rows(int move) { return move == SD_MOVE_RWMH ? 2 : 5; }
@@ -827,9 +829,7 @@ __global__ void __launch_bounds__(64) k_chain_moves(MovesArgs a, int chains_per_
           qf += df * df;
           qb += db * db;
         }
-        const float var = 2.0f * step;
-        const float joint_prop = lp_p - (-0.5f * qf) / var, joint_orig = lp - (-0.5f * qb) / var;
-        log_acc = joint_prop - joint_orig;
+        log_acc = mala_log_acc(lp_p, lp, qf, qb, step);
       }
     } else {
       lp_p = dist_logp_row(a.target, pr);
@@ -845,7 +845,7 @@ __global__ void __launch_bounds__(64) k_chain_moves(MovesArgs a, int chains_per_
         philox4x32_10(cidx, 0u, static_cast<uint32_t>(m), U_STREAM, a.seed_lo, a.seed_hi, r4);
         uu = u01(r4[0]);
       }
-      accept = logf(uu) < log_acc;
+      accept = mh_accept(uu, log_acc);
     }
     if (accept) {
       for (int f = 0; f < d; ++f) {
@@ -854,11 +854,8 @@ __global__ void __launch_bounds__(64) k_chain_moves(MovesArgs a, int chains_per_
       }
       lp = lp_p;
     }
-    if (!ula && a.target_acc > 0.0f) {  // heuristics_step_size (mcmc.py:55-74), per chain
-      if (log_acc - log_target > 0.04879016416943205f) step = step * 1.01f;        // log1p(0.05)
-      if (log_target - log_acc > 0.05129329438755058f) step = step / 1.01f;        // -log1p(-0.05)
-    }
-    if (!ula) last = expf(fminf(0.0f, log_acc));
+    if (!ula && a.target_acc > 0.0f) step = mh_adapt_step(step, log_acc, log_target);
+    if (!ula) last = mh_acc_prob(log_acc);
     if (m >= a.keep_from) {
       if (!ula) acc += last;
       if (a.samples) {

@@ -1241,6 +1241,15 @@ static int pack_tilted(const sdeng_tilted* t, const TiltedLayout& L, float* ws, 
   SD_HIP(sd_launch_tilted_pack(p, s));
   return 0;
 }
+// the shapes, the times and the workspace's pieces: what every tilted kernel takes; the rows to evaluate and the outputs are the caller's
+static TiltedArgs tilted_args(const sdeng_tilted* t, const TiltedLayout& L, float* ws) {
+  TiltedArgs a;
+  memset(&a, 0, sizeof(a));
+  a.M = t->M; a.B = t->rows_per_time; a.d = t->d; a.N = t->n_times; a.K = t->k; a.full = t->full_cov ? 1 : 0;
+  a.use_st = t->use_s_t_scaling ? 1 : 0; a.ntiles = L.ntiles;
+  a.tinfo = t->tinfo; a.pack = ws + L.pack; a.consts = ws + L.consts; a.hbuf = ws + L.hbuf; a.trash = ws + L.trash;
+  return a;
+}
 // the pack (unless reused) and the one launch of either entry point; `rows`: the training instantiation
 static int run_tilted(const sdeng_tilted* t, const TiltedRows* rows, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1250,12 +1259,9 @@ static int run_tilted(const sdeng_tilted* t, const TiltedRows* rows, void* strea
   float* ws = static_cast<float*>(t->workspace);
   const int d = t->d;
   if (!(t->flags & SDENG_FLAG_REUSE_PACK)) SD_TRY(pack_tilted(t, L, ws, s));
-  TiltedArgs a;
-  memset(&a, 0, sizeof(a));
-  a.M = t->M; a.B = t->rows_per_time; a.d = d; a.N = t->n_times; a.K = t->k; a.full = t->full_cov ? 1 : 0;
-  a.use_st = t->use_s_t_scaling ? 1 : 0; a.ntiles = L.ntiles;
-  a.x = t->x; a.tinfo = t->tinfo; a.pack = ws + L.pack; a.consts = ws + L.consts;
-  a.hbuf = (t->grad || rows) ? ws + L.hbuf : nullptr; a.log_prob = t->log_prob; a.grad = t->grad; a.trash = ws + L.trash;
+  TiltedArgs a = tilted_args(t, L, ws);
+  a.x = t->x; a.log_prob = t->log_prob; a.grad = t->grad;
+  if (!t->grad && !rows) a.hbuf = nullptr;  // no backward pass: no pre-activations kept
   if (rows) SD_HIP(sd_launch_tilted_train(a, *rows, tiles_exact(d), L.grid, L.waves, s));
   else SD_HIP(sd_launch_tilted(a, tiles_exact(d), L.grid, L.waves, s));
   return 0;
@@ -1331,11 +1337,7 @@ extern "C" int sdeng_tilted_moves(const sdeng_tilted* t, const sdeng_tilted_move
   if (mv->n_moves == 0) return 0;
   float* ws = static_cast<float*>(t->workspace);
   if (!(t->flags & SDENG_FLAG_REUSE_PACK)) SD_TRY(pack_tilted(t, L, ws, s));
-  TiltedArgs a;
-  memset(&a, 0, sizeof(a));
-  a.M = t->M; a.B = t->rows_per_time; a.d = t->d; a.N = t->n_times; a.K = t->k; a.full = t->full_cov ? 1 : 0;
-  a.use_st = t->use_s_t_scaling ? 1 : 0; a.ntiles = L.ntiles;
-  a.tinfo = t->tinfo; a.pack = ws + L.pack; a.consts = ws + L.consts; a.hbuf = ws + L.hbuf; a.trash = ws + L.trash;
+  const TiltedArgs a = tilted_args(t, L, ws);  // x, log_prob and grad stay null: the chain state is in m
   TiltedMovesArgs m;
   memset(&m, 0, sizeof(m));
   m.x = mv->x; m.grad = mv->grad; m.lp = mv->lp; m.step = mv->step; m.prop = ws + ml.prop; m.gprop = ws + ml.gprop;

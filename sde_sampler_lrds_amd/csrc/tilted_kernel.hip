@@ -76,22 +76,7 @@ int sd_launch_tilted_pack(const TiltedPackArgs& a, hipStream_t s) {
   return static_cast<int>(hipGetLastError());
 }
 
-template <bool TRAIN>
-static int launch_tilted_nt(const TiltedArgs& a, const TiltedRows& rows, int NT, int grid, int waves, hipStream_t s) {
-  switch (NT) {
-    case 1: return launch_tilted<1, TRAIN>(a, rows, grid, waves, s);
-    case 2: return launch_tilted<2, TRAIN>(a, rows, grid, waves, s);
-    case 3: return launch_tilted<3, TRAIN>(a, rows, grid, waves, s);
-    case 4: return launch_tilted<4, TRAIN>(a, rows, grid, waves, s);
-    case 5: return launch_tilted<5, TRAIN>(a, rows, grid, waves, s);
-    case 6: return launch_tilted<6, TRAIN>(a, rows, grid, waves, s);
-    case 7: return launch_tilted<7, TRAIN>(a, rows, grid, waves, s);
-    case 8: return launch_tilted<8, TRAIN>(a, rows, grid, waves, s);
-  }
-  return static_cast<int>(hipErrorInvalidValue);
-}
-
 int sd_launch_tilted(const TiltedArgs& a, int NT, int grid, int waves, hipStream_t s) {
   const TiltedRows none = {};
-  return launch_tilted_nt<false>(a, none, NT, grid, waves, s);
+  return launch_tilted<false>(a, none, NT, grid, waves, s);
 }

@@ -12,7 +12,7 @@ from sde_sampler_lrds_amd import engine as E
 from sde_sampler_lrds_amd.additions import ebm_mle
 from sde_sampler_lrds_amd.additions.mcmc import heuristics_step_size, mala_step, ula_step
 from tests import tilted_cases as tc
-from tests.test_gpu_tilted import KEEP, LEVELS, CHAINS, MARGIN, SAMPLER_SEED, on_gpu, run_sampler
+from tests.test_gpu_tilted import KEEP, LEVELS, CHAINS, MARGIN, SAMPLER_SEED, _mods, on_gpu, run_sampler
 
 pytestmark = pytest.mark.gpu
 STEP, TARGET = 0.02, 0.75
@@ -120,7 +120,7 @@ def test_one_move_against_the_host_composition(case, unadjusted, gpu):
 def test_carried_state_is_the_evaluation_at_the_final_state(case, gpu):
     """After K = 4 moves the lp / grad that come out against E.tilted_eval at the very same x_out, in tilted_cases.err; bound: 2 x MARGIN x
     the case's stored reference-float32 error (each side is held to MARGIN x that error against float64 by the parity test).  The two
-    kernels are not required to agree bit for bit (measured: they do, profiles/tilted_moves_parity.log)."""
+    kernels call the same walk (csrc/tilted_kernel.hpp), so they also agree bit for bit."""
     fx, net, t, x, lp, grad = start(case, gpu)
     torch.manual_seed(11)
     got = moves(net, t, x, lp, grad, 4, target_acceptance=TARGET)
@@ -131,6 +131,31 @@ def test_carried_state_is_the_evaluation_at_the_final_state(case, gpu):
           f"(bound {b_grad:.3e}, ratio {e_grad / b_grad:.3f})  bit-equal: {torch.equal(got['lp'], lp_e) and torch.equal(got['grad'], grad_e)}")
     assert torch.isfinite(got["x"]).all() and not torch.equal(got["x"], x)
     assert e_lp <= b_lp and e_grad <= b_grad
+    assert torch.equal(got["lp"], lp_e) and torch.equal(got["grad"], grad_e)
+
+
+@pytest.mark.parametrize("prior", tc.WALK_PRIORS)
+@pytest.mark.parametrize("nt", range(1, 9))
+def test_every_instance_carries_the_evaluation_bit_for_bit(nt, prior, gpu):
+    """tilted_cases.walk_spec: every k_tilted_moves<NT> and k_tilted_eval<NT> instance over a diagonal and an eigen-form prior, at a d whose
+    last quad is partly pad, on three tiles that straddle the times (15 pad rows).  Four MALA moves with injected (z, u): the state stays
+    finite and moves, and the lp / grad carried out are E.tilted_eval at the final x bit for bit -- the move kernel and the evaluation
+    call one walk -- as is the log-density-only evaluation (no backward pass)."""
+    spec = tc.walk_spec(nt, prior)
+    net = tc.build(spec, *_mods())
+    t, x = tc.draw_inputs(spec, net)
+    net, t, x = net.to(gpu).requires_grad_(False), t.to(gpu), x.to(gpu)
+    assert x.shape == (33, 16 * nt - 3)
+    lp, grad = E.tilted_eval(net, t, x)
+    g = torch.Generator().manual_seed(700 + nt)
+    z, u = torch.randn(4, *x.shape, generator=g).to(gpu), torch.rand(4, x.shape[0], generator=g).to(gpu)
+    got = moves(net, t, x, lp, grad, 4, target_acceptance=TARGET, noise=(z, u))
+    lp_e, grad_e = E.tilted_eval(net, t, got["x"])
+    print(f"\ntilted_moves walk NT={nt} {prior}: d={x.shape[1]} rows moved {int((got['x'] != x).any(1).sum())} of {x.shape[0]}; carried state "
+          f"bit-equal to the evaluation: lp {torch.equal(got['lp'], lp_e)} grad {torch.equal(got['grad'], grad_e)}")
+    assert all(torch.isfinite(got[k]).all() for k in ("x", "lp", "grad")) and not torch.equal(got["x"], x)
+    assert torch.equal(got["lp"], lp_e) and torch.equal(got["grad"], grad_e)
+    assert torch.equal(E.tilted_eval(net, t, got["x"], want_grad=False)[0], lp_e)
 
 
 @pytest.mark.parametrize("case", ["a", "c"])

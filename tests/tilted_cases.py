@@ -26,6 +26,16 @@ CASES = {
     # b with the recipe's all-zero last layer: the net term contributes exactly 0
     "f": dict(d=16, prior="eig", K=3, times=[0.3, 0.7], B=24, sde="vp", t_limit=0.0, st=True, seed=502, zero_last=True),
 }
+WALK_PRIORS = ("diag", "eig")
+
+
+def walk_spec(nt, prior):
+    """A drawn (not stored) case per kernel instance: NT = ``nt`` feature tiles at d = 16 nt - 3 -- never a multiple of four, so the last quad
+    of a row is partly pad --, K = 2 components, three times x 11 rows = 33 rows: three tiles whose boundaries straddle the times, the last
+    with 15 pad rows.  The fixtures reach NT = 1, 4 and 7 only."""
+    return dict(d=16 * nt - 3, prior=prior, K=2, times=[0.2, 0.5, 0.8], B=11, sde="vp", t_limit=0.0, st=prior == "eig", seed=600 + nt)
+
+
 SDE_ARGS = {"vp": dict(diff_coeff_sq_min=0.1, diff_coeff_sq_max=10.0, scale_diff_coeff=1.0, terminal_t=1.0),
             "pbm": dict(diff_coeff=1.5, terminal_t=1.0)}
 

@@ -6,7 +6,8 @@ arithmetic on the same GPU, autograd for the gradient -- what a user had before 
 Shapes: the phi^4 replica-exchange move (100 levels x 256 chains, d = 100, K = 4 full covariances) and the logistic-regression
 evaluation batch (6 000 rows at one time, d = 61, one Gaussian).  Warm-up, then the median of --reps timed calls (hip events around
 each call, the packed images already cached -- as in a sampler's loop); both sides on the same device in the same process.  The torch
-side works in the same eigen form (one [d,d] product per component and direction), float32, with the time scalars precomputed."""
+side works in the same eigen form (one [d,d] product per component and direction), float32, with the time scalars precomputed.
+SDENG_LIB = another build of the library (tools/probe_lib.py); the "@time" lines (label | median q1 q3, ms) are for an A/B of two builds."""
 import argparse
 import os
 import statistics
@@ -14,7 +15,10 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import probe_lib  # noqa: E402
+
+LIB = probe_lib.select()
 from sde_sampler_lrds_amd import engine as E  # noqa: E402
 from sde_sampler_lrds_amd.eq.sdes import VP  # noqa: E402
 from sde_sampler_lrds_amd.models.mlp import FourierMLP  # noqa: E402
@@ -54,7 +58,12 @@ def timed(fn, reps, warmup=5):
         b.record()
         torch.cuda.synchronize()
         ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms)
+    q = statistics.quantiles(ms, n=4)
+    return statistics.median(ms), min(ms), q[0], q[2]
+
+
+def at_time(label, m):
+    print(f"@time {label} | {m[0]:.4f} {m[2]:.4f} {m[3]:.4f}")
 
 
 def main():
@@ -63,7 +72,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
-    print(f"# device {torch.cuda.get_device_name(0)}; median (min) of {a.reps} calls after 5 warm-up calls, ms")
+    print(f"# device {torch.cuda.get_device_name(0)}; library {LIB}; median (min) of {a.reps} calls after 5 warm-up calls, ms")
     slower = []
     for name, d, K, N, B in (("phi4 replica-exchange move", 100, 4, 100, 256), ("logistic-regression evaluation", 61, 1, 1, 6000)):
         base = FourierMLP(dim=d, activation=torch.nn.GELU(), num_layers=6, channels=128)
@@ -91,6 +100,8 @@ def main():
         print(f"  log_prob + grad   sdeng_tilted_eval {k_both[0]:8.3f} ({k_both[1]:.3f})   torch + autograd {t_both[0]:8.3f} ({t_both[1]:.3f})   "
               f"torch / kernel = {t_both[0] / k_both[0]:.2f}")
         print(f"  log_prob only     sdeng_tilted_eval {k_lp[0]:8.3f} ({k_lp[1]:.3f})")
+        at_time(f"eval {name}, log_prob + grad", k_both)
+        at_time(f"eval {name}, log_prob only", k_lp)
         if k_both[0] > t_both[0]:
             slower.append(name)
     print("# the kernel is slower than the torch composition at: " + (", ".join(slower) if slower else "neither shape"))

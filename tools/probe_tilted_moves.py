@@ -12,7 +12,8 @@ The swap step (two evaluations) and the samplers' bookkeeping are in every timin
 interleaved in the same process -- host loop, one launch with torch's noise, one launch with Philox noise -- after a warm-up of each;
 a timing is a host clock around a call that ends in a device synchronise.  Reported: median, minimum and the quartiles of --reps calls;
 a variant counts as slower than the host loop when its median exceeds the host loop's by more than the host loop's own interquartile
-range."""
+range.  SDENG_LIB = another build of the library (tools/probe_lib.py); the "@time" lines (label | median q1 q3, ms) are for an A/B of two
+builds."""
 import argparse
 import os
 import statistics
@@ -21,7 +22,10 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import probe_lib  # noqa: E402
+
+LIB = probe_lib.select()
 from sde_sampler_lrds_amd.additions import ebm_mle  # noqa: E402
 from sde_sampler_lrds_amd.eq.sdes import VP  # noqa: E402
 from sde_sampler_lrds_amd.models.mlp import FourierMLP  # noqa: E402
@@ -60,7 +64,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
-    print(f"# device {torch.cuda.get_device_name(0)}; {MOVES} local moves per call; median (min; quartiles) of {a.reps} interleaved calls after 3 warm-up calls each, ms")
+    print(f"# device {torch.cuda.get_device_name(0)}; library {LIB}; {MOVES} local moves per call; median (min; quartiles) of {a.reps} interleaved calls after 3 warm-up calls each, ms")
     slower = []
     for name, d, K, full, N, B in SHAPES:
         net = make_net(d, K, full, g, dev)
@@ -99,6 +103,8 @@ def main():
         for vname, _, _ in VARIANTS:
             med, lo, q1, q3 = quartiles(ms[vname])
             print(f"  {vname:26s} {med:9.3f} ({lo:.3f}; {q1:.3f} .. {q3:.3f})   host loop / this = {host[0] / med:.2f}")
+            if vname != "host loop":
+                print(f"@time moves {name}, {vname} | {med:.4f} {q1:.4f} {q3:.4f}")
             if med > host[0] + (host[3] - host[2]):
                 slower.append(f"{name} [{vname}]")
     ebm_mle.NATIVE_MOVES, ebm_mle.NATIVE_NOISE = True, False

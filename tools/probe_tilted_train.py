@@ -9,7 +9,8 @@ twice the rows (positives + negatives in one call), and the logistic-regression 
 Loss: mean(E) + 0.1 mean(E^2) (the trainer's, with reg_val).  Warm-up, then the median and minimum of --reps timed calls (events around
 each call, packed images cached); both sides in the same process.  The split: the launch alone (tilted_vjp), the evaluation launch
 without the arrays (tilted_eval with grad: the same walk), the products alone (tilted_param_grads on arrays already there); the round
-trip of the arrays is the launch minus the evaluation (written once) plus what the products spend reading them."""
+trip of the arrays is the launch minus the evaluation (written once) plus what the products spend reading them.
+SDENG_LIB = another build of the library (tools/probe_lib.py); the "@time" lines are for an A/B of two builds, as in probe_tilted_eval.py."""
 import argparse
 import os
 import sys
@@ -18,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from probe_tilted_eval import timed  # noqa: E402
+from probe_tilted_eval import LIB, at_time, timed  # noqa: E402
 from sde_sampler_lrds_amd import engine as E  # noqa: E402
 from sde_sampler_lrds_amd.eq.sdes import VP  # noqa: E402
 from sde_sampler_lrds_amd.models.mlp import FourierMLP  # noqa: E402
@@ -49,7 +50,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
-    print(f"# device {torch.cuda.get_device_name(0)}; median (min) of {a.reps} calls after 5 warm-up calls, ms")
+    print(f"# device {torch.cuda.get_device_name(0)}; library {LIB}; median (min) of {a.reps} calls after 5 warm-up calls, ms")
     slower = []
     for name, d, K, N, B in (("phi4 trainer, positives", 100, 4, 100, 256), ("phi4 trainer, positives + negatives", 100, 4, 100, 512),
                              ("logistic-regression batch", 61, 1, 1, 6000)):
@@ -92,6 +93,7 @@ def main():
         print(f"  split of the HIP path       sdeng_tilted_vjp launch {launch[0]:.3f} ({launch[1]:.3f})   [sdeng_tilted_eval with grad, no arrays: "
               f"{evalu[0]:.3f} ({evalu[1]:.3f}); writing the arrays: {launch[0] - evalu[0]:+.3f}]   products + time embedding {prods[0]:.3f} ({prods[1]:.3f})   "
               f"rest (loss, autograd bookkeeping) {hip[0] - launch[0] - prods[0]:.3f}")
+        at_time(f"train {name}, sdeng_tilted_vjp launch", launch)
         if hip[0] > tor[0]:
             slower.append(name)
     print("# the HIP path is slower than the torch composition at: " + (", ".join(slower) if slower else "no shape"))
