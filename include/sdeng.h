@@ -548,7 +548,7 @@ size_t sdeng_tilted_vjp_workspace_bytes(const sdeng_tilted* desc);
  * Errors, all before any launch: SDENG_E_INVALID for what sdeng_tilted_eval rejects in the descriptor (but its three ignored pointers), a
  * null `mv` or state pointer, n_moves < 0, keep_from outside [0, n_moves], exactly one of z / u for an adjusted move; SDENG_E_UNSUPPORTED
  * as sdeng_tilted_eval; SDENG_E_WORKSPACE.  Workspace (sdeng_tilted_moves_workspace_bytes): the packed images where sdeng_tilted_eval
- * keeps them (the three entry points share them), per-wave slots of six layers (the five pre-activations and the time embedding), then
+ * keeps them (every tilted entry point shares them), per-wave slots of six layers (the five pre-activations and the time embedding), then
  * the proposal and proposal-score rows, 2 x [M,d]. */
 typedef struct sdeng_tilted_moves_state {
   int32_t n_moves, keep_from, unadjusted, reserved;
@@ -560,6 +560,45 @@ typedef struct sdeng_tilted_moves_state {
 } sdeng_tilted_moves_state;
 int sdeng_tilted_moves(const sdeng_tilted* desc, const sdeng_tilted_moves_state* mv, void* stream);
 size_t sdeng_tilted_moves_workspace_bytes(const sdeng_tilted* desc);
+
+/* RDS over an energy-based reference (ref_type 'nn', solver/oc.py:577-592): one whole simulate() loop of EIReferenceSDELoss /
+ * DDPMLikeReferenceSDELoss (SDENG_FORM_LIN; losses/oc.py:444-510, :584-651, eq/sdes.py:532-555) or EMReferenceSDELoss (SDENG_FORM_EM;
+ * losses/oc.py:218-296) whose reference_ctrl is the score net(t, x) of a tilted potential (models/reparam.py:478-482) -- in the reference one
+ * autograd pass through the 6 x 128 net per step, here all N steps in ONE launch (and one small launch ahead of it for the time embeddings
+ * of the N step times).  Per step k, with the row coef[k] of the table above and the density of sdeng_tilted_eval:
+ *     ref = grad log p_ref(t_k, x_k)      t_k = tinfo[k][0] (the caller passes the times of coef[k][0]); the score of sdeng_tilted_eval at that
+ *                                         row, bit for bit (the kernel calls the same walk)
+ *     u   = clip(FourierMLP(t_k, x_k), clip_model)      ClippedCtrl, models/reparam.py:33-43, models/mlp.py:99-143
+ *     z   = noise_in[k], or the Philox normals of stream 0 with counter (particle0 + p, feature/4, k, 0): sdeng_philox_normal_steps replays them
+ *     then the update and the running cost of SDENG_FORM_LIN / SDENG_FORM_EM exactly as sdeng_simulate forms them (the Ito term with SDENG_FLAG_ITO).
+ * `ref` carries the net, the prior, d, M = the B particles of this shard, n_times = N, tinfo [N][5] at the step times, the workspace and
+ * SDENG_FLAG_REUSE_PACK; its rows_per_time, x, log_prob and grad are ignored.  Terminal costs are NOT added: the caller adds log p_ref(x_N)
+ * (sdeng_tilted_eval at eps: WrapperDistrNN.log_prob, distr/base.py:186-198) and -log pi~(x_N) (sdeng_dist_eval) to rnd_out
+ * (losses/oc.py:290, :505, :645).  No Philox stream is taken beyond stream 0.
+ * Errors, all before any launch: SDENG_E_INVALID for what sdeng_tilted_eval rejects in `ref` (but its ignored fields), a null `run`, a
+ * null coef / x_in / x_out / rnd_out, N < 1 or N != ref->n_times, a malformed drift net; SDENG_E_UNSUPPORTED (reason in
+ * sdeng_last_error) as sdeng_tilted_eval, for a control other than ClippedCtrl, a form other than LIN / EM and any flag but
+ * SDENG_FLAG_ITO (REMOVE_REF, CTRL_NOISE, CTRL_DROPOUT and SPLIT_TILES are named); SDENG_E_WORKSPACE.
+ * Workspace (sdeng_tilted_simulate_workspace_bytes): the packed images where sdeng_tilted_eval keeps them (the four entry points share
+ * them), the per-wave pre-activations, the packed drift net and its N time embeddings, the EBM's N time embeddings [N][128], the score
+ * rows [B,d] and two state rows [B,d] (used without xs_out). */
+typedef struct sdeng_tilted_rds {
+  int32_t form;             /* SDENG_FORM_LIN or SDENG_FORM_EM                                       */
+  uint32_t flags;           /* SDENG_FLAG_ITO or 0                                                   */
+  int32_t N;                /* steps (= ref->n_times)                                                */
+  int32_t reserved;
+  const float* coef;        /* [N][SDENG_NCOEF]                                                      */
+  sdeng_net net;            /* the drift net, ctrl_kind SDENG_CTRL_CLIPPED                           */
+  uint64_t seed;            /* Philox key                                                            */
+  int64_t particle0;        /* global index of this shard's first particle                           */
+  const float* x_in;        /* [B,d]                                                                 */
+  const float* noise_in;    /* [N,B,d] or NULL                                                       */
+  float *x_out, *rnd_out;   /* [B,d], [B]                                                            */
+  float* xs_out;            /* [N+1,B,d] or NULL                                                     */
+  float* ref_out;           /* [N,B,d] or NULL: the reference score the kernel used at every step (for tests) */
+} sdeng_tilted_rds;
+int sdeng_tilted_simulate(const sdeng_tilted* ref, const sdeng_tilted_rds* run, void* stream);
+size_t sdeng_tilted_simulate_workspace_bytes(const sdeng_tilted* ref, const sdeng_tilted_rds* run);
 
 #ifdef __cplusplus
 }

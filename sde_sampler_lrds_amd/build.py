@@ -98,7 +98,7 @@ def _launcher(fam, nt, params):
 def sources():
     os.makedirs(GEN, exist_ok=True)
     srcs = [os.path.join(CSRC, n) for n in ("sdeng_api.hip", "prep_kernels.hip", "metric_kernels.hip", "cmcd_inst.hip", "tilted_kernel.hip",
-                                            "tilted_train_inst.hip", "tilted_moves_inst.hip")]
+                                            "tilted_train_inst.hip", "tilted_moves_inst.hip", "tilted_rds_inst.hip")]
     for unit, insts in UNITS.items():
         headers = sorted({FAMILIES[fam][0] for fam, _, _ in insts})
         body = "".join(f'#include "../{h}"\n' for h in headers) + "".join(

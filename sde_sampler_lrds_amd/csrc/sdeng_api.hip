@@ -20,6 +20,7 @@
 #include "cmcd_adjoint_kernel.hpp"
 #include "metric_kernels.hpp"
 #include "tilted_kernel.hpp"
+#include "tilted_rds.hpp"
 
 int sd_launch_logreg_images(const float* X, const float* y, int n, int dw, int NT, float* image, float* y_pad, hipStream_t s);
 int sd_launch_pack_square(const float* P, const float* loc, int d, int NT, float* out, float* loc_pad, hipStream_t s);
@@ -1181,13 +1182,15 @@ static TiltedLayout tilted_layout(const sdeng_tilted* t, bool train = false) {
   return L;
 }
 // `who`: the entry point, for the messages; `train`: sdeng_tilted_vjp, where log_prob and grad may both be absent; `moves`:
-// sdeng_tilted_moves, which ignores x, log_prob and grad (the chain state is in its own argument block)
-static int check_tilted(const sdeng_tilted* t, const char* who = "tilted_eval", bool train = false, bool moves = false) {
+// sdeng_tilted_moves, which ignores x, log_prob and grad (the chain state is in its own argument block); `sim`: sdeng_tilted_simulate,
+// which ignores those three and rows_per_time (M particles walk n_times steps)
+static int check_tilted(const sdeng_tilted* t, const char* who = "tilted_eval", bool train = false, bool moves = false, bool sim = false) {
   if (!t) return fail(SDENG_E_INVALID, "%s: null descriptor", who);
   if (t->abi_version != SDENG_ABI_VERSION) return fail(SDENG_E_INVALID, "ABI version %d, library has %d", t->abi_version, SDENG_ABI_VERSION);
   if (t->d < 1 || t->d > 128) return fail(SDENG_E_INVALID, "%s: d = %d outside [1, 128]", who, t->d);
   if (t->k < 1 || t->k > TL_KMAX) return fail(SDENG_E_INVALID, "%s: k = %d components outside [1, %d]", who, t->k, TL_KMAX);
-  if (t->M < 1 || t->n_times < 1 || t->rows_per_time < 1 || static_cast<long long>(t->n_times) * t->rows_per_time != t->M)
+  if (sim && (t->M < 1 || t->n_times < 1)) return fail(SDENG_E_INVALID, "%s: M = %d particles, n_times = %d steps", who, t->M, t->n_times);
+  if (!sim && (t->M < 1 || t->n_times < 1 || t->rows_per_time < 1 || static_cast<long long>(t->n_times) * t->rows_per_time != t->M))
     return fail(SDENG_E_INVALID, "%s: M = %d rows is not n_times * rows_per_time = %d * %d", who, t->M, t->n_times, t->rows_per_time);
   if (static_cast<long long>(t->M) * t->d >= (1ll << 31)) return fail(SDENG_E_UNSUPPORTED, "%s: rows * d >= 2^31", who);
   if (t->num_layers != 6 || t->channels != TL_H)
@@ -1346,5 +1349,78 @@ extern "C" int sdeng_tilted_moves(const sdeng_tilted* t, const sdeng_tilted_move
   const Seed sd = split_seed(mv->seed);
   m.seed_lo = sd.lo; m.seed_hi = sd.hi; m.chain0 = mv->chain0;
   SD_HIP(sd_launch_tilted_moves(a, m, tiles_exact(t->d), L.grid, L.waves, s));
+  return 0;
+}
+
+// ---- the RDS step loop over an energy-based reference: tilted_rds_inst.hip -------------------------------------------------------------
+// workspace: the layout of an evaluation with grad (so the packed images are where sdeng_tilted_eval keeps them), then the packed drift net,
+// its time embeddings, the EBM's time embeddings, the score rows and the two ping-pong state rows
+struct TiltedRdsLayout {
+  TiltedLayout L;
+  size_t wpack, temb, te_tab, score, ping, total;  // floats
+};
+static TiltedRdsLayout tilted_rds_layout(const sdeng_tilted* t, const sdeng_tilted_rds* r) {
+  TiltedRdsLayout rl;
+  rl.L = tilted_layout(t, true);
+  size_t o = rl.L.total;
+  const size_t rows = align64(static_cast<size_t>(t->M) * t->d);
+  rl.wpack = o; o += align64(sd_pack_floats(tiles_exact(t->d)));
+  rl.temb = o; o += align64(static_cast<size_t>(r->N) * SD_H);
+  rl.te_tab = o; o += align64(static_cast<size_t>(r->N) * TL_H);
+  rl.score = o; o += rows;
+  rl.ping = o; o += 2 * rows;
+  rl.total = o;
+  return rl;
+}
+static int check_tilted_rds(const sdeng_tilted* t, const sdeng_tilted_rds* r) {
+  const char* who = "tilted_simulate";
+  SD_TRY(check_tilted(t, who, false, true, true));
+  if (!r) return fail(SDENG_E_INVALID, "%s: null run", who);
+  if (!r->coef || !r->x_in || !r->x_out || !r->rnd_out) return fail(SDENG_E_INVALID, "%s: coef, x_in, x_out and rnd_out are all required", who);
+  if (r->N < 1 || r->N != t->n_times) return fail(SDENG_E_INVALID, "%s: N = %d steps (>= 1, and the n_times = %d of the reference's time table)", who, r->N, t->n_times);
+  if (r->net.ctrl_kind != SDENG_CTRL_CLIPPED)
+    return fail(SDENG_E_UNSUPPORTED, "%s: ClippedCtrl around the FourierMLP only (ctrl_kind %d given): a Score / Lerp / CancelDrift control has no "
+                "kernel over an energy-based reference", who, r->net.ctrl_kind);
+  if (r->form != SDENG_FORM_LIN && r->form != SDENG_FORM_EM)
+    return fail(SDENG_E_UNSUPPORTED, "%s: SDENG_FORM_LIN and SDENG_FORM_EM only (form %d given; no EUBO or CMCD loop over an energy-based reference)", who, r->form);
+  if (r->flags & ~SDENG_FLAG_ITO)
+    return fail(SDENG_E_UNSUPPORTED, "%s: flags 0x%x: SDENG_FLAG_ITO only (REMOVE_REF, CTRL_NOISE, CTRL_DROPOUT and SPLIT_TILES have no kernel over an "
+                "energy-based reference; initial and terminal costs are the caller's)", who, r->flags);
+  SD_TRY(check_net(r->net));
+  return 0;
+}
+extern "C" size_t sdeng_tilted_simulate_workspace_bytes(const sdeng_tilted* t, const sdeng_tilted_rds* r) {
+  if (check_tilted_rds(t, r)) return 0;
+  return tilted_rds_layout(t, r).total * sizeof(float);
+}
+extern "C" int sdeng_tilted_simulate(const sdeng_tilted* t, const sdeng_tilted_rds* r, void* stream) {
+  SD_TRY(check_tilted_rds(t, r));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const TiltedRdsLayout rl = tilted_rds_layout(t, r);
+  const TiltedLayout& L = rl.L;
+  const size_t need = rl.total * sizeof(float);
+  if (!t->workspace || t->workspace_bytes < need)
+    return fail(SDENG_E_WORKSPACE, "tilted_simulate: workspace %zu bytes, need %zu", t->workspace_bytes, need);
+  float* ws = static_cast<float*>(t->workspace);
+  if (!(t->flags & SDENG_FLAG_REUSE_PACK)) SD_TRY(pack_tilted(t, L, ws, s));
+  TiltedArgs a = tilted_args(t, L, ws);  // x, log_prob and grad stay null: the state is in m
+  a.B = t->M;  // every row of a step shares the step's time
+  sdeng_desc nd;  // what the drift net's packer and its time embedding read of a descriptor
+  memset(&nd, 0, sizeof(nd));
+  nd.d = t->d; nd.N = r->N; nd.coef = r->coef; nd.net = r->net;
+  const int DT = tiles_exact(t->d);
+  SD_TRY(pack_net(&nd, DT, ws + rl.wpack, nullptr, s));
+  const float* no_stheta;  // (ClippedCtrl: no score model)
+  SD_TRY(embed_times(&nd, r->N, false, 0.0f, ws + rl.temb, nullptr, &no_stheta, s));
+  SD_HIP(sd_launch_tilted_rds_times(a, ws + rl.te_tab, s));
+  TiltedRdsArgs m;
+  memset(&m, 0, sizeof(m));
+  m.form = r->form; m.flags = r->flags; m.N = r->N; m.coef = r->coef;
+  m.wpack = ws + rl.wpack; m.temb = ws + rl.temb; m.te_tab = ws + rl.te_tab; m.clip_model = r->net.clip_model;
+  const Seed sd = split_seed(r->seed);
+  m.seed_lo = sd.lo; m.seed_hi = sd.hi; m.particle0 = r->particle0;
+  m.x_in = r->x_in; m.noise_in = r->noise_in; m.x_out = r->x_out; m.rnd_out = r->rnd_out; m.xs_out = r->xs_out; m.ref_out = r->ref_out;
+  m.ping = ws + rl.ping; m.score = ws + rl.score;
+  SD_HIP(sd_launch_tilted_rds(a, m, DT, L.grid, L.waves, s));
   return 0;
 }

@@ -193,8 +193,8 @@ SD_INLINE void tl_grad_axpy(float* grad, float* trash, uint32_t row, int d, bool
   }
 }
 
-// ---- The walk of one 16-row tile, phase by phase.  k_tilted_eval<NT, TRAIN> below and k_tilted_moves<NT> (tilted_moves_inst.hip) call
-// these four phases and hold no walk of their own, so the order of the floating-point statements inside a phase is shared: with
+// ---- The walk of one 16-row tile, phase by phase.  k_tilted_eval<NT, TRAIN> below, k_tilted_moves<NT> (tilted_moves_inst.hip) and
+// k_tilted_rds<NT> (tilted_rds_inst.hip) call these four phases and hold no walk of their own, so the order of the floating-point statements inside a phase is shared: with
 // -ffp-contract=off the same statements give the same bits, and the state a move kernel carries is the evaluation at that state.
 // Every tl_stage is met by every wave of the workgroup, idle waves (`active` false) and pad rows included: the conditions around a
 // staging are uniform over the workgroup, the conditions on `active` are around the arithmetic only.

@@ -75,6 +75,23 @@ class Distribution(torch.nn.Module):
         return self.unnorm_log_prob(x)
 
 
+class WrapperDistrNN(Distribution):
+    """distr/base.py:186-198: an energy-based model at one time ``t`` as a distribution -- the reference distribution of RDS with
+    ``ref_type='nn'`` (solver/oc.py:584), ``t`` = eps, the start of the time grid.  ``log_prob`` of a tilted potential of this package is
+    one ``engine.tilted_eval`` launch; the time travels as the (1, 1) tensor made here once, so its table is read back once."""
+
+    def __init__(self, dim, net, t):
+        super().__init__(dim=dim, log_norm_const=0.0)
+        self.net = net
+        self.t = t
+        self._t_row = torch.as_tensor(t).reshape(1, 1)
+
+    def unnorm_log_prob(self, x: torch.Tensor) -> torch.Tensor:
+        if hasattr(self.net, "_eval"):  # this package's potentials take one time for all rows
+            return self.net.unnorm_log_prob(self._t_row.to(x.device) if self._t_row.device != x.device else self._t_row, x)
+        return self.net.unnorm_log_prob(self.t * torch.ones((x.shape[0], 1), device=x.device), x)
+
+
 class ModeWeightMetrics:
     """The sample-based diagnostics of the multi-modal targets (``distr/gauss.py:245-293``, ``distr/rings.py:111-160``,
     ``distr/checkerboard.py:93-140``): entropy of the empirical mode weights, their KL / TV distance to the true weights and the share

@@ -1030,7 +1030,7 @@ def ctrl_forward(ctrl, t: float, x: torch.Tensor, score_gain=1.0, lerp_w=0.0):
 # energy-based (tilted-potential) references: GMMTitledPotential / GaussTiltedPotential (models/reparam.py:277-606)
 # ------------------------------------------------------------------------------------------------
 _TILTS = {"dot": L.TILT_DOT, "sq_norm": L.TILT_SQ_NORM}
-_TILTED_CLASSES = ("GMMTitledPotential", "GaussTiltedPotential")
+_TILTED_CLASSES = R.TILTED_CLASSES
 
 
 def _tilted_mixture(net):
@@ -1253,6 +1253,61 @@ def tilted_moves(net, t, x, lp, grad, step, n_moves, *, keep_from=0, unadjusted=
     _tilted_workspace(net, d, need, device)
     _check_supported(launch())
     return samples, acc, last
+
+
+def tilted_simulate(net, ctrl, coef: torch.Tensor, tinfo: torch.Tensor, x: torch.Tensor, *, form=None, flags=None, seed=0, particle0=0,
+                    noise=None, return_traj=False, want_ref=False):
+    """sdeng_tilted_simulate: all N steps of an RDS ``simulate()`` loop over the energy-based reference ``net`` in one launch
+    (include/sdeng.h) -- the reference score of ``tilted_eval`` at (t_k, x_k), the control ``ctrl`` (ClippedCtrl around the 4 x 64
+    FourierMLP), the noise of Philox stream 0 keyed by ``seed`` and ``particle0`` + row (``philox_noise`` replays it) or ``noise``
+    [N,B,d], the update and the running cost of ``form`` (``L.FORM_LIN``, the default, or ``L.FORM_EM``; ``flags``: ``L.FLAG_ITO``, the
+    default, or 0).  ``coef`` [N, NCOEF] is the step loop's table (``coef_table``), ``tinfo`` [N, 5] the reference's times at
+    ``coef[:, 0]`` (``tilted_times``).  Terminal costs are the caller's.  Refusals are ``tilted_eval``'s and the entry point's own.
+    Returns (x_N [B,d], rnd [B,1], xs [N+1,B,d] or None, ref [N,B,d] or None: the reference score the kernel used at every step)."""
+    require_gpu(x)
+    if tilted_needs_param_grad(net):
+        raise UnsupportedByEngine("tilted_simulate computes no gradient with respect to the reference net's parameters: freeze them "
+                                  "(RDS.change_reference_type('nn') does) or call it under torch.no_grad()")
+    lib = L.lib()
+    device, keep = x.device, []
+    xin = _f32c(x)
+    if xin.dim() != 2:
+        raise ValueError("tilted_simulate: x must be [B, d]")
+    B, dim = xin.shape
+    coef = coef.detach().to(device=device, dtype=torch.float32).contiguous()
+    tdev = tinfo.detach().to(device=device, dtype=torch.float32).contiguous()
+    N = coef.shape[0]
+    if coef.shape != (N, L.NCOEF) or tdev.shape != (N, 5):
+        raise ValueError(f"tilted_simulate: coef must be [N, {L.NCOEF}] and tinfo [N, 5], got {tuple(coef.shape)} and {tuple(tdev.shape)}")
+    keep += [xin, coef, tdev]
+    d = tilted_desc(net, device, keep)
+    if d.d != dim:
+        raise ValueError(f"tilted_simulate: x has {dim} features, the potential {d.d}")
+    d.M, d.n_times, d.rows_per_time, d.tinfo = B, N, B, tdev.data_ptr()
+    run = L.TiltedRds()
+    run.form = L.FORM_LIN if form is None else int(form)
+    run.flags = L.FLAG_ITO if flags is None else int(flags)
+    run.N, run.coef = N, coef.data_ptr()
+    run.net = net_desc(ctrl, device, keep)
+    run.seed, run.particle0 = int(seed) & 0xFFFFFFFFFFFFFFFF, int(particle0)
+    x_out = torch.empty_like(xin)
+    rnd = torch.empty(B, 1, dtype=torch.float32, device=device)
+    xs = torch.empty(N + 1, B, dim, dtype=torch.float32, device=device) if return_traj else None
+    ref = torch.empty(N, B, dim, dtype=torch.float32, device=device) if want_ref else None
+    nz = None
+    if noise is not None:
+        nz = noise.detach().to(device=device, dtype=torch.float32).contiguous()
+        if nz.shape != (N, B, dim):
+            raise ValueError(f"tilted_simulate: noise must be [N,B,d] = {(N, B, dim)}, got {tuple(nz.shape)}")
+    run.x_in, run.noise_in, run.x_out, run.rnd_out = xin.data_ptr(), _ptr(nz), x_out.data_ptr(), rnd.data_ptr()
+    run.xs_out, run.ref_out = _ptr(xs), _ptr(ref)
+    launch = lambda: lib.sdeng_tilted_simulate(C.byref(d), C.byref(run), _stream_ptr(device))  # noqa: E731
+    need = lib.sdeng_tilted_simulate_workspace_bytes(C.byref(d), C.byref(run))
+    if need == 0:
+        _check_supported(launch())  # the descriptors are rejected: fetch the code and the reason
+    _tilted_workspace(net, d, need, device)
+    _check_supported(launch())
+    return x_out, rnd, xs, ref
 
 
 def tilted_vjp(net, t, x: torch.Tensor, want_grad=False, per_row_times=False):

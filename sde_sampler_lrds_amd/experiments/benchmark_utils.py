@@ -16,6 +16,7 @@ from ..distr.gauss import BracketTwoModes, ManyModes, TwoModes, TwoModesFull
 from ..distr.logistic_regression import LogisticRegression
 from ..distr.phi_four import PhiFour
 from ..distr.rings import Rings
+from .. import routes as R
 from ..engine import UnsupportedByEngine
 from ..eval.sinkhorn import Sinkhorn
 from ..models.reparam import RemoveReferenceCtrl
@@ -160,14 +161,19 @@ def make_model(solver_type, ref_type, loss_type, integrator_type, model_type, ti
                training_details, optim_details=None, n_steps=100, force_base_zero_init=False, use_ema=False, force_vp20=False,
                force_vp_cosine=False, compute_samples_based_metrics=True, force_T_cosine=None, device="cuda"):
     """experiments/benchmark_utils.py:96-265.  Every combination the reference rejects is rejected here with the same exception
-    (``validate_make_model_args``); of those it accepts, the ones without a HIP kernel -- UNet drift nets, 'nn' references -- raise
+    (``validate_make_model_args``); of those it accepts, the ones without a HIP kernel -- UNet drift nets, 'nn' references
+    whose ``solver_details['net']`` is not a tilted potential -- raise
     ``UnsupportedByEngine`` (a NotImplementedError) AFTER that validation, never a silently different sampler."""
     validate_make_model_args(solver_type, ref_type, loss_type, integrator_type, model_type, time_type, solver_details, target_details,
                              training_details, force_base_zero_init, force_vp20, force_vp_cosine)
     if model_types[model_type] in ("score_unet", "basic_unet"):
         raise UnsupportedByEngine(f"model_type {model_type}: the UNet drift net (models/mnist_unet.py) has no HIP kernel")
     if ref_type == "nn" and "ref" in solver_type:
-        raise UnsupportedByEngine("'nn' references need autograd of an energy net inside every step (models/reparam.py:478-482): no HIP kernel")
+        net = (solver_details or {}).get("net")
+        if net is None or R.name_of(net) not in R.TILTED_CLASSES:
+            raise UnsupportedByEngine("'nn' references on the HIP path are tilted potentials: solver_details['net'] must be a GMMTitledPotential / "
+                                      f"GaussTiltedPotential (models/reparam.py:277-606), got {R.name_of(net) if net is not None else 'no net'}; "
+                                      "any other energy net needs autograd inside every step (models/reparam.py:478-482): no HIP kernel")
 
     cls, prior, sde, loss_kind = _SOLVERS[solver_types[solver_type]]
     prior, sde = dict(prior), (dict(sde) if sde else None)
@@ -212,6 +218,8 @@ def make_model(solver_type, ref_type, loss_type, integrator_type, model_type, ti
         elif ref_type == "gmm":
             model.change_reference_type(ref_type="gmm", weights=solver_details["weights_ref"], means=solver_details["means_ref"],
                                         variances=solver_details["variances_ref"])
+        elif ref_type == "nn":  # benchmark_utils.py:246-251
+            model.change_reference_type(ref_type="nn", net=solver_details["net"], eps=torch.tensor(float(ts["start"])))
     if "cmcd" in solver_type and ref_type == "gaussian":
         model.update_prior(mean=solver_details["mean"], var=solver_details["var"])
     if time_type == "snr":

@@ -75,6 +75,7 @@ class BaseOCLoss:
         self.split_tiles = False  # True: small batches (<= _lib.SPLIT_TILES_MAX_B = 8 192, the library's own gate) ask for the low-latency kernels (SDENG_FLAG_SPLIT_TILES; fp32-round-off, not bit, equal to the standard kernel); the solvers switch it on (cfg 'split_tiles', default True)
         self.dist = None  # torch.distributed of a sharded run: eval() then returns global estimators and globally normalised weights
         self._perturb = {}  # coefficient-table options of the control perturbation, set for the step loop of a log-variance training call
+        self._nn_times = None  # an energy-based ('nn') reference: (coefficient table, net, its time table [N, 5] on the device) of the last grid
 
     # ---- reference surface -----------------------------------------------------------------
     def filter(self, rnd, samples=None):
@@ -351,6 +352,10 @@ class BaseOCLoss:
     def _simulate(self, ts, x, *, terminal_unnorm_log_prob, reference_log_prob=None, initial_log_prob=None, form,
                   flags, use_ema, return_traj, noise, ref=("none", {}), coef_kw=None):
         E.require_gpu(x)
+        if ref[0] == "nn":  # an energy-based reference: the step loop of sdeng_tilted_simulate
+            return self._simulate_nn(ts, x, ref[1]["net"], terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
+                                     initial_log_prob=initial_log_prob, form=form, flags=flags, use_ema=use_ema, return_traj=return_traj,
+                                     noise=noise, coef_kw=coef_kw)
         if isinstance(x, E.InitialDraw) and (form == L.FORM_EUBO or (initial_log_prob is not None and E.resolve_logp(initial_log_prob) is None)):
             x = self._x0(x)  # an opaque initial log-density needs x0 as a tensor; the noising loops start from data anyway
         device = x.device
@@ -400,6 +405,53 @@ class BaseOCLoss:
         assert rnd.shape == (x.shape[0], 1)
         return x_out, rnd, xs
 
+    def _nn_refusal(self, ctrl, form=None):
+        """Why this loss cannot run over an energy-based ('nn') reference -- the reason, in words -- or None.  The kernel of
+        sdeng_tilted_simulate holds the reference score and a ClippedCtrl; everything that would need the reference score inside the
+        control, a perturbed control or the noising direction has no kernel there."""
+        rec = R.describe_ctrl(ctrl)
+        if rec.wrapper is not None:
+            return "RemoveReferenceCtrl over an energy-based ('nn') reference: the kernel does not subtract the EBM's score from the control"
+        if rec.kind != L.CTRL_CLIPPED:
+            return (f"{R.name_of(rec.ctrl)} over an energy-based ('nn') reference: the one-launch step loop holds a ClippedCtrl only "
+                    "(Score / Lerp / CancelDrift controls need the target score next to the EBM walk)")
+        if self.sde_ctrl_noise is not None or self.sde_ctrl_dropout is not None or self._perturb:
+            return "sde_ctrl_noise / sde_ctrl_dropout over an energy-based ('nn') reference: the kernel has no control-perturbation stage"
+        if form == L.FORM_EUBO:
+            return "compute_eubo over an energy-based ('nn') reference: no noising loop is built around the EBM walk"
+        return None
+
+    def _simulate_nn(self, ts, x, net, *, terminal_unnorm_log_prob, reference_log_prob, initial_log_prob, form, flags, use_ema, return_traj,
+                     noise, coef_kw):
+        """``_simulate`` over an energy-based reference (RDS.change_reference_type('nn'), solver/oc.py:577-585): one
+        sdeng_tilted_simulate launch for the N steps, then the terminal costs with the launches that exist -- ``reference_log_prob``
+        (WrapperDistrNN.log_prob: sdeng_tilted_eval at eps) and the target's log-density (sdeng_dist_eval) -- as losses/oc.py:290, :505, :645."""
+        ctrl = self._ctrl(use_ema)
+        why = self._nn_refusal(ctrl, form)
+        if why is None and initial_log_prob is not None:
+            why = "an initial log-density over an energy-based ('nn') reference: the RDS losses have none"
+        if why is None:
+            why = E.tilted_refusal(net, x.device)
+            why = why and f"energy-based ('nn') reference: {why}"
+        if why is not None:
+            raise E.UnsupportedByEngine(why)
+        x = self._x0(x)
+        coef = self._coef(ts, x.device, **(coef_kw or {}))
+        hit = self._nn_times
+        if hit is None or hit[0] is not coef or hit[1] is not net:  # the reference's times of this grid: read back once per table
+            t_net = coef[:, 0].detach().to("cpu")
+            hit = self._nn_times = (coef, net, E.tilted_times(net, t_net, t_net.numel(), per_row=True)[2].to(x.device))
+        x_out, rnd, xs, _ = E.tilted_simulate(net, ctrl, coef, hit[2], x, form=form, flags=flags & L.FLAG_ITO, seed=int(self.seed),
+                                              particle0=int(self.particle0), noise=noise, return_traj=return_traj)
+        term = 0.0  # rnd += reference_log_prob(x) - terminal_unnorm_log_prob(x): the difference first, as upstream
+        if reference_log_prob is not None:
+            term = term + self._logp(reference_log_prob, x_out)
+        if terminal_unnorm_log_prob is not None:
+            term = term - self._logp(terminal_unnorm_log_prob, x_out)
+        rnd += term
+        assert rnd.shape == (x.shape[0], 1)
+        return x_out, rnd, xs
+
     def _no_train(self, change_sde_ctrl):
         if change_sde_ctrl:
             raise E.UnsupportedByEngine("simulate(change_sde_ctrl=True) is the reference's internal training call: log-variance training "
@@ -433,7 +485,12 @@ class EMReferenceSDELoss(BaseOCLoss):
         def sim(xx):
             return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
                                  change_sde_ctrl=False, return_traj=True, use_ema=False)
-        with_ref = E.resolve_reference(self.reference_ctrl)[0] != "none"
+        ref_kind = E.resolve_reference(self.reference_ctrl)[0]
+        with_ref = ref_kind != "none"
+        if ref_kind == "nn":  # an energy-based reference: log-variance training of a ClippedCtrl only, refused before any rollout
+            why = R.KL_OVER_NN if self.method in ("kl", "kl_ito") else self._nn_refusal(self.generative_ctrl)
+            if why is not None:
+                raise E.UnsupportedByEngine(why)
         if self.method in ("kl", "kl_ito"):  # :364-394 with change_sde_ctrl = False; the Ito term is always part of these losses (:284, :499)
             return self._kl_loss(ts, x, sim,
                                  lambda xn: reference_log_prob(xn).view(-1, 1) - terminal_unnorm_log_prob(xn).view(-1, 1),
@@ -447,6 +504,8 @@ class EMReferenceSDELoss(BaseOCLoss):
         ref = E.resolve_reference(self.reference_ctrl)
         if ref[0] == "none":
             raise E.UnsupportedByEngine("compute_eubo needs a reference control (RDS losses)")
+        if ref[0] == "nn":
+            raise E.UnsupportedByEngine(R.KL_OVER_NN if self.method in ("kl", "kl_ito") else self._nn_refusal(self._ctrl(use_ema), L.FORM_EUBO))
         kind = "eubo_ei" if self.kind == "ei" else "eubo_em"
         x_out, rnd, _ = self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
                                        form=L.FORM_EUBO, flags=0, use_ema=use_ema, return_traj=False, noise=noise, ref=ref,

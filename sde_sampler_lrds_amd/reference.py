@@ -1,5 +1,6 @@
 """Reference drifts of RDS (solver/oc.py:513-592 ``change_reference_type`` + ``reference_ctrl``): the
-score of a Gaussian / Gaussian-mixture reference noised to time t (eq/sdes.py:265-279, 329-345).
+score of a Gaussian / Gaussian-mixture reference noised to time t (eq/sdes.py:265-279, 329-345), or of an
+energy-based model (``EnergyReference``, ref_type 'nn').
 
 ``MarginalReference`` is a callable ``(t, x) -> [B,d]`` (torch, host-side use) that also exposes
 ``reference_distr_utils`` / ``ref_type`` exactly like the reference's RDS solver does, which is what the HIP
@@ -8,7 +9,32 @@ from __future__ import annotations
 
 import torch
 
+from .distr.base import WrapperDistrNN
 from .distr.gauss import score_gauss, score_gauss_full, score_mog, score_mog_full
+
+
+class EnergyReference(torch.nn.Module):
+    """``ref_type='nn'`` (solver/oc.py:577-585): the score of an energy-based model, a GMMTitledPotential / GaussTiltedPotential whose
+    parameters are frozen here as the reference does.  The same surface as ``MarginalReference``: ``reference_distr_utils`` (``{'net': net}``,
+    what ``routes.resolve_reference`` reads), ``reference_distr`` (``WrapperDistrNN`` at ``eps``) and the callable ``(t, x) -> [B,d]`` for
+    host-side use; the step loop evaluates the score in its own kernel (sdeng_tilted_simulate)."""
+
+    ref_type = "nn"
+
+    def __init__(self, net, eps, dim):
+        super().__init__()
+        for p in net.parameters():
+            p.requires_grad_(False)
+        self.net, self.dim = net, dim
+        self.register_buffer("eps", torch.as_tensor(eps).detach().clone(), persistent=False)
+        self.reference_distr_utils = {"net": net}
+
+    @property
+    def reference_distr(self):
+        return WrapperDistrNN(dim=self.dim, net=self.net, t=self.eps)
+
+    def forward(self, t, x):
+        return self.net(t=t.view((1, 1)).expand((x.shape[0], -1)), x=x)
 
 
 class MarginalReference(torch.nn.Module):

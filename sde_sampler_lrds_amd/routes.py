@@ -37,8 +37,11 @@ def dist_kind(obj, score_only=False):
             "Checkerboard": L.DIST_CHECKERBOARD}.get(n)
 
 
+TILTED_CLASSES = ("GMMTitledPotential", "GaussTiltedPotential")  # models/reparam.py:277-606, of this package or of the reference
+
+
 def resolve_reference(reference_ctrl):
-    """``reference_ctrl`` callable -> ('none'|'gaussian'|'gmm', params).  Recognises the bound ``RDS.reference_ctrl`` (solver/oc.py:590-592 +
+    """``reference_ctrl`` callable -> ('none'|'gaussian'|'gmm'|'nn', params).  Recognises the bound ``RDS.reference_ctrl`` (solver/oc.py:590-592 +
     ``reference_distr_utils``) and this package's ``MarginalReference`` objects."""
     if reference_ctrl is None:
         return "none", {}
@@ -50,6 +53,11 @@ def resolve_reference(reference_ctrl):
         return "gmm", utils  # diagonal [K,d], full [K,d,d] or the eigen form (D, P): ref_desc picks the kernel
     if "x_init" in utils:
         return "gaussian", utils  # diagonal [d], a covariance matrix [d,d] or its eigen form (D, P)
+    if "net" in utils:
+        if name_of(utils["net"]) in TILTED_CLASSES:
+            return "nn", utils  # the step loop over an energy-based reference (sdeng_tilted_simulate); engine.tilted_refusal's findings are raised at the first launch
+        raise UnsupportedByEngine(f"EBM ('nn') references on the HIP path are tilted potentials (GMMTitledPotential / GaussTiltedPotential): "
+                                  f"{name_of(utils['net'])} needs autograd inside the step")
     raise UnsupportedByEngine("EBM ('nn') references need autograd inside the step: not on the HIP path")
 
 
@@ -171,10 +179,16 @@ def lv_route(loss):
     return ("graphed" if loss.graph_training and plain else "eager"), ctrl
 
 
+KL_OVER_NN = "KL training differentiates the reference score: second order in the energy net"
+
+
 def kl_route(loss, reference_ctrl=None) -> str:
     """'native' | 'fused' | 'stepwise': the adjoint of a KL training call (BaseOCLoss._kl_loss) whose reference drift is ``reference_ctrl`` (resolved
     first: an opaque callable raises whatever the route)."""
-    if diagonal_reference(*resolve_reference(reference_ctrl)) and loss.native_adjoint and kl_native(loss.generative_ctrl):
+    ref = resolve_reference(reference_ctrl)
+    if ref[0] == "nn":
+        raise UnsupportedByEngine(KL_OVER_NN)
+    if diagonal_reference(*ref) and loss.native_adjoint and kl_native(loss.generative_ctrl):
         return "native"
     return "fused" if loss.fused_training and _own(loss.generative_ctrl, L.CTRL_CLIPPED) else "stepwise"
 

@@ -22,7 +22,9 @@ from ..losses import oc as losses
 from ..models.mlp import FourierMLP, TimeEmbed
 from ..models.reparam import CancelDriftCtrl, ClippedCtrl, LerpCtrl, ScoreCtrl
 from ..models import utils as mutils
-from ..reference import MarginalReference
+from .. import routes as R
+from ..reference import EnergyReference, MarginalReference
+from ..routes import UnsupportedByEngine
 from ..utils.common import Results, clip_and_log, get_timesteps
 
 LOSSES = {name: getattr(losses, name) for name in (
@@ -358,8 +360,15 @@ class RDS(_ReferenceLogProbSolver):
             self._reference = MarginalReference(self.sde, "gaussian", x_init=mean, var_init=var)
         elif ref_type == "gmm":
             self._reference = MarginalReference(self.sde, "gmm", means_init=means, variances_init=variances, weights_init=weights)
+        elif ref_type == "nn":  # solver/oc.py:577-585: an energy-based reference, parameters frozen
+            if net is None or R.name_of(net) not in R.TILTED_CLASSES:
+                raise UnsupportedByEngine(f"Reference type nn: net must be a GMMTitledPotential / GaussTiltedPotential (the energy-based references "
+                                          f"with a HIP step loop), got {R.name_of(net) if net is not None else None}")
+            if eps is None:
+                raise ValueError("Reference type nn: eps (the time of the reference distribution, close to 0) is required")
+            self._reference = EnergyReference(net, eps, self.prior.loc.shape[-1])
         else:
-            raise NotImplementedError(f"Reference type {ref_type}: EBM references need autograd per step (no HIP kernel).")
+            raise NotImplementedError(f"Reference type {ref_type} is unknown.")
         dev = getattr(self, "device", None)
         if dev is not None:
             self._reference.to(dev)
@@ -378,3 +387,9 @@ class RDS(_ReferenceLogProbSolver):
         sd.update({f"ref_{k}": v for k, v in self.reference_distr_utils.items()})
         sd["ref_type"] = self.ref_type
         return sd
+
+    def load_state_dict(self, sd):
+        """solver/oc.py:641-666 for the energy-based reference: ``ref_net`` comes back as the reference at the start of the training grid."""
+        super().load_state_dict(sd)
+        if sd.get("ref_type") == "nn":
+            self.change_reference_type(ref_type="nn", net=sd["ref_net"], eps=self.train_timesteps()[0])
