@@ -81,7 +81,7 @@ SD_INLINE void cmcd_eval(const CmcdArgs& a, const f32x4 (&x)[NT], int ki, float 
 #pragma unroll
       for (int t = 0; t < NT; ++t) {  // one output tile at a time: 2*KB A-operand vectors live instead of 2*KB*NT
         f32x4 ps[1] = {zero}, pm[1] = {zero};
-        dense_pre_buf<KB, 1>(dh, dl, ps, pm, image_rsrc(a.prec_pack, NT * KB * 2 * 1024), static_cast<uint32_t>(t) * KB * 2 * 1024, lane);
+        dense_pre_buf<KB, 1>(dh, dl, ps, pm, image_rsrc(a.prec_pack, sd_image_bytes(NT, NT)), static_cast<uint32_t>(t) * sd_image_bytes(1, NT), lane);
         fold_lo<1>(ps, pm);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -171,7 +171,7 @@ SD_INLINE void cmcd_eval(const CmcdArgs& a, const f32x4 (&x)[NT], int ki, float 
       f32x4 pv;
       if (full_prior) {  // GaussFull: -P (w - mu)   distr/gauss.py:129-135
         f32x4 ps[1] = {zero}, pm[1] = {zero};
-        dense_pre_buf<KB, 1>(dh, dl, ps, pm, image_rsrc(a.prec_pack, NT * KB * 2 * 1024), static_cast<uint32_t>(t) * KB * 2 * 1024, lane);
+        dense_pre_buf<KB, 1>(dh, dl, ps, pm, image_rsrc(a.prec_pack, sd_image_bytes(NT, NT)), static_cast<uint32_t>(t) * sd_image_bytes(1, NT), lane);
         fold_lo<1>(ps, pm);
         pv = f32x4{-ps[0][0], -ps[0][1], -ps[0][2], -ps[0][3]};
       } else if (diag_prior) {  // Gauss.score (score_gauss, distr/gauss.py:124-126)

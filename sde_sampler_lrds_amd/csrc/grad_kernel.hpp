@@ -11,7 +11,7 @@
 // and the parameter gradients are six skinny GEMMs over the rows -- dW_out = d_out^T a2, dW_2 = d2^T a1, dW_1 = d1^T a0, dW_in = d0^T x,
 // bias gradients = column sums, time-embedding cotangent = sum_b d0 -- which the host forms from the per-row arrays this kernel writes.
 // One wave = 16 rows, same register layout as the step loop: every product is a split-f16 MFMA chain; the transposed products read
-// transposed weight images (k_pack_mlp with `transpose`: W_out^T is an input-layer-shaped matrix, W_in^T an output-layer-shaped one).
+// transposed weight images (transposed jobs of k_pack_images: W_out^T is an input-layer-shaped matrix, W_in^T an output-layer-shaped one).
 // Range: a cotangent row is scaled by a per-row power of two to ~2^9 before each transposed product and scaled back after (the backward
 // pass is linear in the cotangent) -- gradients of 1e-6 magnitude keep fp32's relative accuracy through the f16 split.
 #pragma once
@@ -189,7 +189,7 @@ SD_INLINE void vjp_tile(const VjpArgs& a, const float* lds, const float* lds_t, 
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       f32x4 o[1] = {zero}, mx[1] = {zero};
-      dense_pre<2, 1>(hs.h, hs.l, o, mx, reinterpret_cast<const f16x8*>(a.wpack_t + sd_off_wout(NT) + t * 2 * 512), lane);
+      dense_pre<2, 1>(hs.h, hs.l, o, mx, reinterpret_cast<const f16x8*>(a.wpack_t + sd_off_wout(NT) + t * sd_image_floats(1, SD_HT)), lane);
       fold_lo<1>(o, mx);
       gx[t] = o[0] * back;
       __builtin_amdgcn_sched_barrier(0);

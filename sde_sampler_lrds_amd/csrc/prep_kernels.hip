@@ -1,5 +1,5 @@
 // Small per-call kernels around the persistent simulate kernel (gfx950):
-//   k_pack_mlp      nn.Linear weights -> LDS image of MFMA A operands          (models/mlp.py:99-143 parameters)
+//   k_pack_images   nn.Linear weights -> split-f16 images of MFMA A operands   (models/mlp.py:99-143 parameters)
 //   k_time_embed    TimeEmbed.forward for all N step times at once              (models/mlp.py:85-96)
 //   k_ref_tables    noised reference marginals per step                          (eq/sdes.py:208-248, 281-307)
 //   k_dist_tables   static tables of a diagonal Gaussian / mixture               (distr/gauss.py:67-73, 217-221)
@@ -12,95 +12,44 @@
 #include "prep_kernels.hpp"
 
 // ------------------------------------------------------------------------------------------------
-// weights -> packed LDS image.  One thread per packed float.
+// matrices -> split-f16 images (image_format.hpp): the drift net's (forward and transposed), the CMCD prior's precision, the tilted net's.
+// SD_PACK_SPLIT blocks per job, one thread per 16-bit half; every block of a job forms the job's largest entry itself (the matrices are
+// a few thousand floats, read through L2), the first stores the scale and the bias.
 // ------------------------------------------------------------------------------------------------
-// One thread per 16-bit half of the image.  Block (to, kb), part (0 = hi, 1 = lo), lane, j:
-//   w = W[16 to + (lane & 15)][16 (2 kb + j/4) + 4 (lane >> 4) + j%4];  hi = f16(w);  lo = f16((w - hi) * 2^11)
-// Per-matrix power-of-two scale (sim_common.hpp SD_N_SCALES): four blocks, one matrix each.
-__global__ void __launch_bounds__(256) k_weight_scales(PackArgs a) {
+#define SD_PACK_SPLIT 16
+static_assert(sizeof(PackJobs) <= 4096, "the job list travels as a kernel argument");
+__global__ void __launch_bounds__(256) k_pack_images(const PackJobs a) {
   __shared__ float red[256];
-  float* sc = a.out + sd_off_scales(a.NT);
-  {
-    const int l = blockIdx.x;
-    const float* W = l == 0 ? a.w_in : (l == 1 ? a.w_h1 : (l == 2 ? a.w_h2 : a.w_out));
-    const int n = (l == 0 || l == 3) ? SD_H * a.d : SD_H * SD_H;
+  const int tid = threadIdx.x, part_of_job = blockIdx.x % SD_PACK_SPLIT;
+  const PackJob& j = a.job[blockIdx.x / SD_PACK_SPLIT];
+  float scale = 1.0f;
+  if (j.scale_src) {
     float m = 0.0f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-      const float v = __builtin_fabsf(W[i]);
-      m = (v <= 3.0e38f) ? fmaxf(m, v) : m;  // non-finite weights do not decide the scale (they poison the result either way)
-    }
-    red[threadIdx.x] = m;
+    for (int i = tid; i < j.scale_n; i += 256) m = sd_scale_maxabs(m, j.scale_src[i]);
+    red[tid] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+      if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
       __syncthreads();
     }
-    if (threadIdx.x == 0) {
-      const float mx = red[0];
-      int e = 0;
-      if (mx > 0.0f && (mx < 9.765625e-4f || mx >= 16384.0f)) {  // outside [2^-10, 2^14): normalise the largest entry to [1, 2)
-        int ex;
-        frexpf(mx, &ex);  // mx = f * 2^ex, f in [0.5, 1)
-        e = 1 - ex;
-        e = e > 100 ? 100 : (e < -100 ? -100 : e);
-      }
-      sc[l] = ldexpf(1.0f, e);
-      sc[4 + l] = ldexpf(1.0f, -e);
-    }
-    __syncthreads();
-  }
-}
-
-__global__ void k_pack_mlp(PackArgs a) {
-  const int NT = a.NT;
-  const float* scales = a.transpose ? a.scales : a.out + sd_off_scales(NT);  // written by k_weight_scales, launched ahead of this kernel
-  const int n_half = sd_lds_weight_floats(NT) * 2;
-  const int n_bias = a.transpose ? 0 : 3 * 64 + 16 * NT;
-  _Float16* img = reinterpret_cast<_Float16*>(a.out);
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n_half + n_bias; idx += gridDim.x * blockDim.x) {
-    if (idx < n_half) {
-      const int fl = idx >> 1;  // float-equivalent offset, to find the layer
-      const float* W;
-      int n_out, n_in, KB, base, layer;
-      if (fl < sd_off_wh1(NT)) {
-        W = a.w_in; n_out = SD_H; n_in = a.d; KB = sd_kb(NT); base = sd_off_win(NT); layer = 0;
-      } else if (fl < sd_off_wh2(NT)) {
-        W = a.w_h1; n_out = SD_H; n_in = SD_H; KB = 2; base = sd_off_wh1(NT); layer = 1;
-      } else if (fl < sd_off_wout(NT)) {
-        W = a.w_h2; n_out = SD_H; n_in = SD_H; KB = 2; base = sd_off_wh2(NT); layer = 2;
-      } else {
-        W = a.w_out; n_out = a.d; n_in = SD_H; KB = 2; base = sd_off_wout(NT); layer = 3;
-      }
-      const int local = idx - 2 * base;          // half index inside the layer
-      const int j = local & 7;
-      const int lane = (local >> 3) & 63;
-      const int part = (local >> 9) & 1;
-      const int blk = local >> 10;
-      const int kb = blk % KB, to = blk / KB;
-      const int o = 16 * to + (lane & 15);
-      const int i = 16 * (2 * kb + (j >> 2)) + 4 * (lane >> 4) + (j & 3);
-      float w = 0.0f;
-      if (o < n_out && i < n_in) {
-        if (!a.transpose) {
-          w = W[static_cast<size_t>(o) * n_in + i] * scales[layer];  // power of two: exact
-        } else {  // slot `layer` holds the transpose of matrix 3 - layer, stored [n_in x n_out] row-major
-          const float* Wt = layer == 0 ? a.w_out : (layer == 1 ? a.w_h2 : (layer == 2 ? a.w_h1 : a.w_in));
-          w = Wt[static_cast<size_t>(i) * n_out + o] * scales[3 - layer];
-        }
-      }
-      const _Float16 hi = static_cast<_Float16>(w);
-      img[idx] = part == 0 ? hi : static_cast<_Float16>((w - static_cast<float>(hi)) * 2048.0f);
-    } else {
-      const int b = idx - n_half;
-      float v;
-      // biases carry their layer's scale too: they are the initial value of the layer's accumulator
-      if (b < 64) v = a.b_in[b] * scales[0];
-      else if (b < 128) v = a.b_h1[b - 64] * scales[1];
-      else if (b < 192) v = a.b_h2[b - 128] * scales[2];
-      else v = (b - 192 < a.d) ? a.b_out[b - 192] * scales[3] : 0.0f;
-      a.out[sd_off_bias(NT) + b] = v;
+    const int e = sd_scale_exponent(red[0]);
+    scale = ldexpf(1.0f, e);  // power of two: the products below are exact
+    if (j.scale_dst && part_of_job == 0 && tid == 0) {
+      j.scale_dst[0] = scale;
+      j.scale_dst[j.inv_off] = ldexpf(1.0f, -e);
     }
   }
+  _Float16* img = reinterpret_cast<_Float16*>(j.dst);
+  for (int idx = part_of_job * 256 + tid; idx < j.out_tiles * j.k_blocks * SD_BLOCK_HALVES; idx += SD_PACK_SPLIT * 256) {
+    const SdImageCoord c = sd_image_coord(idx, j.k_blocks);
+    float w = 0.0f;
+    if (c.o < j.n_out && c.i < j.n_in)
+      w = (j.transpose ? j.src[static_cast<size_t>(c.i) * j.ld + j.col0 + c.o] : j.src[static_cast<size_t>(c.o) * j.ld + j.col0 + c.i]) * scale;
+    img[idx] = sd_split_part(w, c.part);
+  }
+  // a bias carries its matrix's scale too: it is the initial value of the product's accumulator
+  if (j.bias && part_of_job == 0)
+    for (int i = tid; i < j.bias_pad; i += 256) j.bias_dst[i] = i < j.n_out ? j.bias[i] * scale : 0.0f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -217,8 +166,7 @@ __global__ void __launch_bounds__(128) k_ref_tables(RefTabArgs a) {
 // ------------------------------------------------------------------------------------------------
 // Full-covariance mixture reference per step (eq/sdes.py:228-238 in the reference's own eigen form: covariance_c =
 // U_c diag(lambda_c) U_c^T  =>  noised precision P = U diag(1/(VA + S2 lambda)) U^T, log det = sum log(VA + S2 lambda)).
-// The precision is written directly as the split-f16 MFMA A-operand image the step loop multiplies with (layout of
-// k_pack_mlp: half index -> (to, kb, part, lane, j), element P[16 to + lane%16][16 (2 kb + j/4) + 4 (lane/16) + j%4]).
+// The precision is written directly as the split-f16 MFMA A-operand image the step loop multiplies with (image_format.hpp).
 // grid = N*K blocks of 256 threads.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_ref_full_tables(RefFullArgs a) {
@@ -230,7 +178,7 @@ __global__ void __launch_bounds__(256) k_ref_full_tables(RefFullArgs a) {
   const float VA = a.coef ? a.coef[static_cast<size_t>(k) * SDENG_NCOEF + 10] : 0.0f;
   const float S2 = a.coef ? a.coef[static_cast<size_t>(k) * SDENG_NCOEF + 11] : 1.0f;
   const int KB = sd_kb(a.NT);
-  const int img_floats = a.NT * KB * 512;
+  const int img_floats = sd_image_floats(a.NT, a.NT);
   float ls = 0.0f;
   for (int j = threadIdx.x; j < 128; j += 256) {
     float iv = 0.0f;
@@ -258,25 +206,21 @@ __global__ void __launch_bounds__(256) k_ref_full_tables(RefFullArgs a) {
   const float* U = a.eigvecs + static_cast<size_t>(c) * a.d * a.d;
   _Float16* img = reinterpret_cast<_Float16*>(a.images + blk * img_floats);
   for (int idx = threadIdx.x; idx < img_floats * 2; idx += 256) {
-    const int j8 = idx & 7, lane = (idx >> 3) & 63, part = (idx >> 9) & 1, tb = idx >> 10;
-    const int kb = tb % KB, to = tb / KB;
-    const int o = 16 * to + (lane & 15);
-    const int i = 16 * (2 * kb + (j8 >> 2)) + 4 * (lane >> 4) + (j8 & 3);
+    const SdImageCoord c = sd_image_coord(idx, KB);
     float p = 0.0f;
-    if (o < a.d && i < a.d) {
-      const float* uo = U + static_cast<size_t>(o) * a.d;
-      const float* ui = U + static_cast<size_t>(i) * a.d;
+    if (c.o < a.d && c.i < a.d) {
+      const float* uo = U + static_cast<size_t>(c.o) * a.d;
+      const float* ui = U + static_cast<size_t>(c.i) * a.d;
       for (int j = 0; j < a.d; ++j) p = __builtin_fmaf(uo[j] * invd[j], ui[j], p);
     }
-    const _Float16 hi = static_cast<_Float16>(p);
-    img[idx] = part == 0 ? hi : static_cast<_Float16>((p - static_cast<float>(hi)) * 2048.0f);
+    img[idx] = sd_split_part(p, c.part);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
 // Shared-variance mixture reference on the matrix pipe (RF_GMM_MM): noised marginal mu_k = S m_k, var = VA + S2 v (eq/sdes.py:228-229,
-// 247), centre c = mean_k mu_k.  Per step: centre / 1/var vectors, logit constants, and the two split-f16 A-operand images in the
-// (to, kb, part, lane, 8 halves) layout of k_pack_mlp:  logit image [kt component tiles][KB(NT)]: (mu_k - c) / var ;
+// 247), centre c = mean_k mu_k.  Per step: centre / 1/var vectors, logit constants, and the two split-f16 A-operand images
+// (image_format.hpp):  logit image [kt component tiles][KB(NT)]: (mu_k - c) / var ;
 // mean image [NT feature tiles][KB(kt)]: mu_k - c.   grid = N blocks of 256 threads.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_ref_mm_tables(RefMMArgs a) {
@@ -285,7 +229,7 @@ __global__ void __launch_bounds__(256) k_ref_mm_tables(RefMMArgs a) {
   const float S = a.coef[static_cast<size_t>(k) * SDENG_NCOEF + 9];
   const float VA = a.coef[static_cast<size_t>(k) * SDENG_NCOEF + 10];
   const float S2 = a.coef[static_cast<size_t>(k) * SDENG_NCOEF + 11];
-  const int KBX = sd_kb(a.NT), KBK = (a.kt + 1) / 2;
+  const int KBX = sd_kb(a.NT), KBK = sd_kb(a.kt);
   for (int f = threadIdx.x; f < 128; f += 256) {
     float c = 0.0f, iv = 0.0f;
     if (f < a.d) {
@@ -319,23 +263,18 @@ __global__ void __launch_bounds__(256) k_ref_mm_tables(RefMMArgs a) {
     }
     a.consts[static_cast<size_t>(k) * 64 + c] = b;
   }
-  const int n_logit = a.kt * KBX * 1024, n_mean = a.NT * KBK * 1024;  // halves
+  const int n_logit = sd_mm_logit_floats(a.kt, a.NT) * 2, n_mean = sd_mm_mean_floats(a.kt, a.NT) * 2;  // halves
   _Float16* img = reinterpret_cast<_Float16*>(a.images + static_cast<size_t>(k) * ((n_logit + n_mean) / 2));
   for (int idx = threadIdx.x; idx < n_logit + n_mean; idx += 256) {
     const bool logit = idx < n_logit;
-    const int local = logit ? idx : idx - n_logit, KB = logit ? KBX : KBK;
-    const int j8 = local & 7, lane = (local >> 3) & 63, part = (local >> 9) & 1, blk = local >> 10;
-    const int kb = blk % KB, to = blk / KB;
-    const int o = 16 * to + (lane & 15);
-    const int i = 16 * (2 * kb + (j8 >> 2)) + 4 * (lane >> 4) + (j8 & 3);
-    const int comp = logit ? o : i, f = logit ? i : o;
+    const SdImageCoord c = logit ? sd_image_coord(idx, KBX) : sd_image_coord(idx - n_logit, KBK);
+    const int comp = logit ? c.o : c.i, f = logit ? c.i : c.o;
     float v = 0.0f;
     if (comp < a.K && f < a.d) {
       const float mu = S * a.means[static_cast<size_t>(comp) * a.d + f] - cbar[f];
       v = logit ? mu * ivs[f] : mu;
     }
-    const _Float16 hi = static_cast<_Float16>(v);
-    img[idx] = part == 0 ? hi : static_cast<_Float16>((v - static_cast<float>(hi)) * 2048.0f);
+    img[idx] = sd_split_part(v, c.part);
   }
 }
 
@@ -1059,10 +998,8 @@ int sd_launch_sample_x0(const sdeng_dist& ds, unsigned lo, unsigned hi, long lon
 }
 
 // ---- host-side launch wrappers -------------------------------------------------------------------
-int sd_launch_pack(const PackArgs& a, hipStream_t s) {
-  const int total = sd_lds_weight_floats(a.NT) * 2 + (a.transpose ? 0 : 3 * 64 + 16 * a.NT);
-  if (!a.transpose) hipLaunchKernelGGL(k_weight_scales, dim3(4), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_pack_mlp, dim3((total + 255) / 256), dim3(256), 0, s, a);
+int sd_launch_pack_images(const PackJobs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_images, dim3(a.njobs * SD_PACK_SPLIT), dim3(256), 0, s, a);
   return static_cast<int>(hipGetLastError());
 }
 int sd_launch_time_embed(const TimeEmbedArgs& a, int N, hipStream_t s) {

@@ -5,15 +5,22 @@
 
 #define SD_LOGZ_MAX_BLOCKS 1024
 
-struct PackArgs {
-  int NT, d;
-  const float *w_in, *b_in, *w_h1, *b_h1, *w_h2, *b_h2, *w_out, *b_out;
-  float* out;
-  // transpose = 1: the image of the TRANSPOSED net for the backward products (grad_kernel.hpp): slot of W_in <- W_out^T, W_1 <- W_2^T,
-  // W_2 <- W_1^T, W_out <- W_in^T, each with the power-of-two scale of its own matrix, read from `scales` (the forward image's
-  // scale block); no biases.  transpose = 0: `scales` is ignored (the forward pack computes and stores them).
-  int transpose;
-  const float* scales;
+// One copying job of k_pack_images: a row-major matrix (or a column range of it), or its transpose, -> one split-f16 image
+// (image_format.hpp), with the power-of-two prescale of a matrix of the caller's choice and, scaled alike, a bias vector.
+struct PackJob {
+  const float* src;        // [n_out, ld] row-major from column col0 on; transpose: [n_in, ld], the image is of its transpose
+  const float* scale_src;  // [scale_n] the matrix whose largest entry decides the scale, or nullptr: no scale
+  float* dst;              // the image, [out_tiles][k_blocks] blocks
+  float* scale_dst;        // 2^e here and 2^-e at scale_dst[inv_off], or nullptr: not stored
+  const float* bias;       // [n_out], or nullptr
+  float* bias_dst;         // [bias_pad]: bias * 2^e, 0 from n_out on
+  int ld, col0, n_out, n_in, scale_n, inv_off;
+  int16_t transpose, bias_pad, out_tiles, k_blocks;
+};
+#define SD_PACK_MAX_JOBS 48
+struct PackJobs {
+  int njobs;
+  PackJob job[SD_PACK_MAX_JOBS];
 };
 
 struct TimeEmbedArgs {
@@ -41,7 +48,7 @@ struct RefFullArgs {
   int K, d, dpad, NT;
   const float* coef;  // per-step marginal (cols 9..11); nullptr = the mixture itself at every step
   const float *means, *eigvals, *eigvecs, *weights;
-  float* images;     // [N][K][NT*KB*512]  split-f16 A-operand image of P = U diag(1/(VA + S2 lambda)) U^T
+  float* images;     // [N][K][sd_image_floats(NT, NT)]  split-f16 A-operand image of P = U diag(1/(VA + S2 lambda)) U^T
   float* means_out;  // [N][K][dpad]       S * mean (0 on pad features)
   float* consts;     // [N][K][2]          (0.5 log det, log w)
 };
@@ -52,7 +59,7 @@ struct RefMMArgs {
   int K, d, dpad, NT, kt;     // kt = ceil(K / 16) component tiles (<= 4)
   const float* coef;
   const float *means, *vars, *weights;  // vars: [K][d], all rows equal (row 0 is read)
-  float* images;    // [N][kt*KB(NT)*512 + NT*KB(kt)*512]
+  float* images;    // [N][sd_mm_logit_floats(kt, NT) + sd_mm_mean_floats(kt, NT)]
   float* centre;    // [N][2][dpad]   centre of the noised means, 1/var (0 on pad features)
   float* consts;    // [N][64]        b_k = log w_k - 0.5 sum_f (mu_kf - c_f)^2 / var_f ; -inf on pad components
   float* same_var;  // [1] scratch: k_same_var's verdict on `vars` -- a caller whose shared_var promise is false gets NaN, not a wrong score
@@ -103,7 +110,8 @@ struct TerminalArgs {
   float* rnd;
 };
 
-int sd_launch_pack(const PackArgs& a, hipStream_t s);
+int sd_launch_pack_images(const PackJobs& a, hipStream_t s);
+int sd_launch_logreg_images(const float* X, const float* y, int n, int dw, int NT, float* image, float* y_pad, hipStream_t s);  // cmcd_inst.hip
 int sd_launch_time_embed(const TimeEmbedArgs& a, int N, hipStream_t s);
 int sd_launch_ref_tables(const RefTabArgs& a, int N, hipStream_t s);
 int sd_launch_ref_full_tables(const RefFullArgs& a, int N, hipStream_t s);

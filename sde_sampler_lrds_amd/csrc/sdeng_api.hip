@@ -22,9 +22,6 @@
 #include "tilted_kernel.hpp"
 #include "tilted_rds.hpp"
 
-int sd_launch_logreg_images(const float* X, const float* y, int n, int dw, int NT, float* image, float* y_pad, hipStream_t s);
-int sd_launch_pack_square(const float* P, const float* loc, int d, int NT, float* out, float* loc_pad, hipStream_t s);
-
 // ---- error string ------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, ...) {
@@ -128,7 +125,7 @@ static bool split_eligible(const sdeng_desc* d, int DT) {
 static int share_room(int DT) { return (160 * 1024 - static_cast<int>(sizeof(float)) * sd_lds_weight_floats(DT)) / 2 / static_cast<int>(sizeof(float)); }
 static int mm_piece(int K, int DT) {  // RF_GMM_MM: floats of the larger of the logit / mean images
   const int kt = (K + 15) / 16;
-  return std::max(kt * sd_kb(DT), DT * ((kt + 1) / 2)) * 512;
+  return std::max(sd_mm_logit_floats(kt, DT), sd_mm_mean_floats(kt, DT));
 }
 // Diagonal mixture references with 4 < K <= 64 components that share one variance vector run on the matrix pipe (RF_GMM_MM):
 // forward forms with a ClippedCtrl.  SDENG_REF_MM=0 keeps the vector path (A/B measurements).
@@ -156,11 +153,11 @@ static bool make_layout(const sdeng_desc* d, Layout& L) {
   L.stheta = o; o += align64(d->N + 1);
   const int K = ref_components(d);
   if (d->ref.kind == SDENG_REF_GMM_FULL) {  // precision images + noised means
-    L.ref_tab = o; o += align64(static_cast<size_t>(d->N) * K * DT * sd_kb(DT) * 512 + 256);
+    L.ref_tab = o; o += align64(static_cast<size_t>(d->N) * K * sd_image_floats(DT, DT) + 256);
     L.ref_mean = o; o += align64(static_cast<size_t>(d->N) * K * dpad);
   } else if (use_mm(d, DT)) {  // logit + mean images, centre / 1/var vectors (+ 64 logit constants per step under ref_consts)
     const int kt = (K + 15) / 16;
-    L.ref_tab = o; o += align64(static_cast<size_t>(d->N) * (kt * sd_kb(DT) + DT * ((kt + 1) / 2)) * 512 + 1024);
+    L.ref_tab = o; o += align64(static_cast<size_t>(d->N) * (sd_mm_logit_floats(kt, DT) + sd_mm_mean_floats(kt, DT)) + 1024);
     L.ref_mean = o; o += align64(static_cast<size_t>(d->N) * 2 * dpad);
   } else {
     L.ref_tab = o; o += align64(static_cast<size_t>(d->N) * K * 2 * dpad);
@@ -179,7 +176,7 @@ static bool make_layout(const sdeng_desc* d, Layout& L) {
                          (d->form == SDENG_FORM_CMCD || d->form == SDENG_FORM_CMCD_EUBO || d->net.ctrl_kind != SDENG_CTRL_CLIPPED);
     const int n = lr_used ? d->target.k : 0;
     o += align64(sd_lr_floats(DT, n)) + align64(32 * sd_lr_row_kb(n));
-    if (d->form == SDENG_FORM_CMCD || d->form == SDENG_FORM_CMCD_EUBO) o += align64(DT * sd_kb(DT) * 512) + align64(16 * DT);
+    if (d->form == SDENG_FORM_CMCD || d->form == SDENG_FORM_CMCD_EUBO) o += align64(sd_image_floats(DT, DT)) + align64(16 * DT);
   }
   L.x0 = o;
   if (!d->x_in && !d->x0_out) o += align64(static_cast<size_t>(d->B) * d->d);  // the engine's own x0 draw
@@ -316,18 +313,43 @@ static int check_net(const sdeng_net& n) {
   }
   return 0;
 }
-// the packed image of the net at `out`; with `out_t`, also the transposed image for the backward products (grad_kernel.hpp)
+// one more job of a k_pack_images launch (PackJob, prep_kernels.hpp): the image of src [n_out x n_in] -- or, with `transpose`, of the transpose
+// of src [n_in x n_out] -- unscaled and without a bias; the caller names a scale source and a bias where there is one
+static PackJob& add_pack_job(PackJobs& p, const float* src, int ld, int n_out, int n_in, bool transpose, int out_tiles, int k_blocks, float* dst) {
+  PackJob& j = p.job[p.njobs++];
+  j = PackJob{};
+  j.src = src; j.ld = ld; j.n_out = n_out; j.n_in = n_in; j.transpose = transpose;
+  j.out_tiles = static_cast<int16_t>(out_tiles); j.k_blocks = static_cast<int16_t>(k_blocks); j.dst = dst;
+  return j;
+}
+static void scale_by(PackJob& j, const float* matrix, int n, float* scale_dst = nullptr, int inv_off = 0) {
+  j.scale_src = matrix; j.scale_n = n; j.scale_dst = scale_dst; j.inv_off = inv_off;
+}
+static void with_bias(PackJob& j, const float* bias, float* dst, int padded) {
+  j.bias = bias; j.bias_dst = dst; j.bias_pad = static_cast<int16_t>(padded);
+}
+// the packed image of the net at `out`; with `out_t`, in the same launch the image of the TRANSPOSED net for the backward products
+// (grad_kernel.hpp): slot of W_in <- W_out^T, W_1 <- W_2^T, W_2 <- W_1^T, W_out <- W_in^T, each with the scale of its own matrix; no biases
 static int pack_net(const sdeng_desc* d, int DT, float* out, float* out_t, hipStream_t s) {
   const sdeng_net& n = d->net;
-  PackArgs pk;
-  pk.NT = DT; pk.d = d->d;
-  pk.w_in = n.w_in; pk.b_in = n.b_in; pk.w_h1 = n.w_h1; pk.b_h1 = n.b_h1; pk.w_h2 = n.w_h2; pk.b_h2 = n.b_h2; pk.w_out = n.w_out; pk.b_out = n.b_out;
-  pk.out = out; pk.transpose = 0; pk.scales = nullptr;
-  SD_HIP(sd_launch_pack(pk, s));
-  if (out_t) {
-    pk.out = out_t; pk.transpose = 1; pk.scales = out + sd_off_scales(DT);
-    SD_HIP(sd_launch_pack(pk, s));
+  const int dim = d->d, KBD = sd_kb(DT), KBH = sd_kb(SD_HT);
+  const float* W[4] = {n.w_in, n.w_h1, n.w_h2, n.w_out};
+  const float* b[4] = {n.b_in, n.b_h1, n.b_h2, n.b_out};
+  const int n_out[4] = {SD_H, SD_H, SD_H, dim}, n_in[4] = {dim, SD_H, SD_H, SD_H};
+  const int tiles[4] = {SD_HT, SD_HT, SD_HT, DT}, kbs[4] = {KBD, KBH, KBH, KBH};
+  const int off[4] = {sd_off_win(DT), sd_off_wh1(DT), sd_off_wh2(DT), sd_off_wout(DT)};
+  PackJobs pk;
+  pk.njobs = 0;
+  for (int l = 0; l < 4; ++l) {
+    PackJob& j = add_pack_job(pk, W[l], n_in[l], n_out[l], n_in[l], false, tiles[l], kbs[l], out + off[l]);
+    scale_by(j, W[l], n_out[l] * n_in[l], out + sd_off_scales(DT) + l, 4);
+    with_bias(j, b[l], out + sd_off_bias(DT) + 64 * l, 16 * tiles[l]);
   }
+  for (int l = 0; out_t && l < 4; ++l) {  // slot l has the shape of layer l and holds the transpose of matrix m = 3 - l, stored [n_in x n_out]
+    const int m = 3 - l;
+    scale_by(add_pack_job(pk, W[m], n_out[l], n_out[l], n_in[l], true, tiles[l], kbs[l], out_t + off[l]), W[m], n_out[m] * n_in[m]);
+  }
+  SD_HIP(sd_launch_pack_images(pk, s));
   return 0;
 }
 // time embedding of the drift net at n_times rows of coef (t_direct: at t_value), and the clipped score_model(t) when the control has one
@@ -544,9 +566,12 @@ static int run_cmcd(const SimPlan& p, const sdeng_desc* d, float* ws, SimArgs& a
   memset(&c, 0, sizeof(c));
   float* prec = ws + L.cmcd;
   if (d->target.kind == SDENG_DIST_LOGREG) SD_TRY(prepare_logreg(d, L, ws, DT, a, s, &prec));
-  float* locp = prec + align64(DT * sd_kb(DT) * 512);
+  float* locp = prec + align64(sd_image_floats(DT, DT));
   if (d->prior.kind == SDENG_DIST_GAUSS_FULL) {
-    SD_HIP(sd_launch_pack_square(d->prior.scale, d->prior.loc, d->d, DT, prec, locp, s));
+    PackJobs pk;  // the precision, unscaled, with loc as its padded "bias"
+    pk.njobs = 0;
+    with_bias(add_pack_job(pk, d->prior.scale, d->d, d->d, d->d, false, DT, sd_kb(DT), prec), d->prior.loc, locp, 16 * DT);
+    SD_HIP(sd_launch_pack_images(pk, s));
     c.prec_pack = prec; c.prior_loc = locp;
   } else if (d->prior.kind == SDENG_DIST_ISO_GAUSS) {
     c.iso_loc = d->prior.p0; c.inv_iso_var = 1.0f / d->prior.p3;
@@ -591,8 +616,7 @@ static int prepare_ref(const SimPlan& p, const sdeng_desc* d, float* ws, SimArgs
       SD_HIP(sd_launch_ref_full_tables(r, d->N, s));
     }
     a.ref_mean = ws + L.ref_mean;
-    const int piece = (DT > 4 ? DT / 2 : DT) * sd_kb(DT) * 512;  // floats per staged piece of an image (sim_kernel.hpp FULL_PIECE)
-    a.ref_share = (piece / 256 + SD_WAVES - 1) / SD_WAVES;
+    a.ref_share = (sd_full_piece_floats(DT) / 256 + SD_WAVES - 1) / SD_WAVES;
     return 0;
   }
   if (rf == RF_GMM_MM) {
@@ -1214,16 +1238,16 @@ extern "C" size_t sdeng_tilted_eval_workspace_bytes(const sdeng_tilted* t) {
 // the packed images and constants of the net and the prior, at the head of the workspace of every tilted entry point
 static int pack_tilted(const sdeng_tilted* t, const TiltedLayout& L, float* ws, hipStream_t s) {
   const int d = t->d, H = TL_H;
-  TiltedPackArgs p;
-  memset(&p, 0, sizeof(p));
-  p.pack = ws + L.pack; p.consts = ws + L.consts;
-  p.coeff = t->te_coeff; p.phase = t->te_phase; p.mean_gauss = t->mean_gauss; p.var_gauss = t->var_gauss;
-  p.weights = t->weights; p.means = t->means; p.vars = t->vars; p.d = d; p.K = t->k;
-  int n = 0;
+  float* consts = ws + L.consts;
+  static_assert(TL_NIMG <= SD_PACK_MAX_JOBS, "one job per image slot");
+  PackJobs p;
+  p.njobs = 0;
+  // one matrix (or a column range of it) -> slot `slot`, its scale at TL_C_SCALE / TL_C_INV + slot, its scaled bias at `bias_off`
   auto job = [&](int slot, const float* W, int n_out, int n_in, int ld, int col0, int transpose, int scale_n, const float* bias, int bias_off) {
-    TiltedPackJob& j = p.job[n++];
-    j.src = W; j.scale_src = W; j.bias = bias; j.n_out = n_out; j.n_in = n_in; j.ld = ld; j.col0 = col0; j.transpose = transpose;
-    j.scale_n = scale_n; j.slot = slot; j.bias_off = bias ? bias_off : -1;
+    PackJob& j = add_pack_job(p, W, ld, n_out, n_in, transpose, (n_out + 15) / 16, (n_in + 31) / 32, ws + L.pack + static_cast<size_t>(slot) * TL_SLOT);
+    j.col0 = col0;
+    scale_by(j, W, scale_n, consts + TL_C_SCALE + slot, TL_C_INV - TL_C_SCALE);
+    if (bias) with_bias(j, bias, consts + bias_off, 128);
   };
   job(TL_TE1S, t->te_w1, H, H, 2 * H, 0, 0, 2 * H * H, t->te_b1, TL_C_BTE1);  // the sine and cosine halves share the matrix's scale
   job(TL_TE1C, t->te_w1, H, H, 2 * H, H, 0, 2 * H * H, nullptr, 0);
@@ -1240,8 +1264,11 @@ static int pack_tilted(const sdeng_tilted* t, const TiltedLayout& L, float* ws, 
       job(TL_EIG + 2 * k, P, d, d, d, 0, 1, d * d, nullptr, 0);      // y = P^T z
       job(TL_EIG + 2 * k + 1, P, d, d, d, 0, 0, d * d, nullptr, 0);  // P q
     }
-  p.njobs = n;
-  SD_HIP(sd_launch_tilted_pack(p, s));
+  SD_HIP(sd_launch_pack_images(p, s));
+  TiltedConstArgs c;
+  c.consts = consts; c.coeff = t->te_coeff; c.phase = t->te_phase; c.mean_gauss = t->mean_gauss; c.var_gauss = t->var_gauss;
+  c.weights = t->weights; c.means = t->means; c.vars = t->vars; c.d = d; c.K = t->k;
+  SD_HIP(sd_launch_tilted_consts(c, s));
   return 0;
 }
 // the shapes, the times and the workspace's pieces: what every tilted kernel takes; the rows to evaluate and the outputs are the caller's

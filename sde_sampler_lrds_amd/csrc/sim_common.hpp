@@ -12,7 +12,7 @@
 // (rows = output features, columns = particles).  Because an MFMA's summation index may be permuted as long
 // as both operands agree, that same register group is directly the B operand of the next layer (k-step r of
 // tile t <-> feature feat(t,r,g)), so the whole [d -> 64 -> 64 -> 64 -> d] drift net runs out of registers with
-// no cross-lane traffic; the A operands (weights) are pre-permuted once into an LDS image by k_pack_mlp.
+// no cross-lane traffic; the A operands (weights) are pre-permuted once into an LDS image by k_pack_images.
 //
 // Why 16-particle tiles (an earlier build used 32x32x2 MFMA, 32 particles per wave): the state of a tile is
 // half as many registers per lane (d=128: 32 instead of 64), so the whole step loop at d=128 fits the 256-VGPR
@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "image_format.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -34,25 +35,18 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define SD_THREADS (SD_WAVES * 64)
 #define SD_WAVES_MAX 12    // step-loop instantiations that fit the 168-register budget run 3 waves per SIMD (sim_kernel.hpp sd_waves_of)
 
-// Packed drift-net image.  The GEMMs run on the f16 matrix pipe as a two-piece split (see sim_device.hpp,
-// dense_f16x2): every weight is stored as hi = f16(w) and lo = f16((w - hi) * 2^11).  One block = one
-// (16-output tile, 32-input K-block) = 64 lanes x 8 halves for hi, then the same for lo = 2 KiB = 512 floats.
-//   W_in [4][KB(NT)] blocks, W_h1 [4][2], W_h2 [4][2], W_out [NT][2]; then b_in, b_h1, b_h2 (64 each), b_out (16*NT)
-__host__ __device__ inline int sd_kb(int NT) { return (NT + 1) / 2; }  // 32-feature K-blocks covering NT tiles
-__host__ __device__ inline int sd_off_win(int NT) { return 0; }
-__host__ __device__ inline int sd_off_wh1(int NT) { return 4 * sd_kb(NT) * 512; }
-__host__ __device__ inline int sd_off_wh2(int NT) { return sd_off_wh1(NT) + 4 * 2 * 512; }
-__host__ __device__ inline int sd_off_wout(int NT) { return sd_off_wh2(NT) + 4 * 2 * 512; }
-__host__ __device__ inline int sd_lds_weight_floats(int NT) { return sd_off_wout(NT) + NT * 2 * 512; }
-__host__ __device__ inline int sd_off_bias(int NT) { return sd_lds_weight_floats(NT); }
-// Power-of-two prescale of the four weight matrices (k_weight_scales, prep_kernels.hip): the f16 split v = hi + lo 2^-11 carries fp32's
-// 22+ bits only while |v| sits in f16's NORMAL range, so a matrix whose largest entry is below 2^-10 (the reference initialises the last
-// layer at ~1e-7, models/utils.py:7-22: f16-subnormal) or at / above 2^14 is stored as W * 2^e with max |W| 2^e in [1, 2), its bias as
-// b * 2^e, and the layer's output is multiplied by 2^-e (exact).  Matrices already in range keep e = 0 and the old bits.
-// Behind the biases: scale[4] = 2^e per layer (in, h1, h2, out), then inv[4] = 2^-e.
+// Packed drift-net image (the format: image_format.hpp), one image per layer and the vectors behind them:
+//   W_in [4 x NT tiles], W_h1 [4 x 4], W_h2 [4 x 4], W_out [NT x 4]; then b_in, b_h1, b_h2 (64 each), b_out (16*NT); then the
+//   power-of-two prescales of the four matrices: scale[4] = 2^e per layer (in, h1, h2, out), then inv[4] = 2^-e.
+__host__ __device__ constexpr int sd_off_win(int NT) { return 0; }
+__host__ __device__ constexpr int sd_off_wh1(int NT) { return sd_image_floats(SD_HT, NT); }
+__host__ __device__ constexpr int sd_off_wh2(int NT) { return sd_off_wh1(NT) + sd_image_floats(SD_HT, SD_HT); }
+__host__ __device__ constexpr int sd_off_wout(int NT) { return sd_off_wh2(NT) + sd_image_floats(SD_HT, SD_HT); }
+__host__ __device__ constexpr int sd_lds_weight_floats(int NT) { return sd_off_wout(NT) + sd_image_floats(NT, SD_HT); }
+__host__ __device__ constexpr int sd_off_bias(int NT) { return sd_lds_weight_floats(NT); }
 #define SD_N_SCALES 8
-__host__ __device__ inline int sd_off_scales(int NT) { return sd_off_bias(NT) + 3 * 64 + 16 * NT; }
-__host__ __device__ inline int sd_pack_floats(int NT) { return sd_off_scales(NT) + SD_N_SCALES; }
+__host__ __device__ constexpr int sd_off_scales(int NT) { return sd_off_bias(NT) + 3 * 64 + 16 * NT; }
+__host__ __device__ constexpr int sd_pack_floats(int NT) { return sd_off_scales(NT) + SD_N_SCALES; }
 // per-wave LDS copy of one step's reference table [K][2][dpad]; used while K*2*dpad <= SD_REFTAB_FLOATS
 #define SD_REFTAB_FLOATS 1024
 // workgroup-shared copy of a larger mixture's table (RF_GMM_BIG): `share` chunks of 1 KiB per wave, two buffers
@@ -114,7 +108,7 @@ struct SimArgs {
   int ref_kc;               //   components per staged piece of the table (>= ref_k: the whole table in one piece)
   const float* ref_tab;     // [N][K][2][dpad]
   const float* ref_consts;  // [N][K][2]  (0.5*sum log var, log w)
-  const float* ref_mean;      // RF_GMM_FULL: [N][K][dpad] noised means (ref_tab then holds the precision images [N][K][NT*KB*512])
+  const float* ref_mean;      // RF_GMM_FULL: [N][K][dpad] noised means (ref_tab then holds the precision images [N][K][sd_image_floats(NT, NT)])
   const float* ref_same_var;  // [1] 1.0: all components share one variance vector (written by k_ref_tables)
   float ref_c1;             // 0.5*d*log(2*pi)
   DistDev target;         // in-loop target score (ScoreCtrl / LerpCtrl / CMCD)

@@ -73,11 +73,9 @@ SD_INLINE f32x4 load_tile4(const float* base, int t, int g) { return *reinterpre
 //
 // K-block kb covers feature tiles 2kb, 2kb+1: lane (p,g) contributes its 8 registers of those two tiles as the
 // 8 k-values of its group, k-slot (g, j) <-> feature 16 (2kb + j/4) + 4 g + j%4; the weights are stored in the
-// same permutation (k_pack_mlp).  `w` image: 16-byte vectors, index ((to*KB + kb)*2 + part)*64 + lane.
+// same permutation (image_format.hpp).  `w` image: 16-byte vectors, index ((to*KB + kb)*2 + part)*64 + lane.
 // ----------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-#define SD_LO_SCALE 2048.0f
-#define SD_LO_INV 4.8828125e-04f
 
 // One pair of values -> packed (hi, lo) halves in 6 instructions: v_cvt_pk_f16_f32 (round to nearest even), two
 // v_fma_mix_f32 that subtract the f16 halves from the fp32 values exactly (v*1.0 - hi with the f16 operand read in
@@ -210,8 +208,8 @@ SD_INLINE void dense_pre_buf(const f16x8 (&xh)[KB], const f16x8 (&xl)[KB], f32x4
     f16x8 ah[TO], al[TO];
 #pragma unroll
     for (int to = 0; to < TO; ++to) {
-      const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(img, voff, static_cast<int>(tile_bytes) + ((to * KB + kb) * 2 + 0) * 1024, 0);
-      const u32x4 vl = __builtin_amdgcn_raw_buffer_load_b128(img, voff, static_cast<int>(tile_bytes) + ((to * KB + kb) * 2 + 1) * 1024, 0);
+      const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(img, voff, static_cast<int>(tile_bytes) + ((to * KB + kb) * 2 + 0) * SD_PART_BYTES, 0);
+      const u32x4 vl = __builtin_amdgcn_raw_buffer_load_b128(img, voff, static_cast<int>(tile_bytes) + ((to * KB + kb) * 2 + 1) * SD_PART_BYTES, 0);
       ah[to] = __builtin_bit_cast(f16x8, vh);
       al[to] = __builtin_bit_cast(f16x8, vl);
     }
@@ -378,14 +376,13 @@ SD_INLINE float row_downscale(const f32x4 (&v)[T]) {
 template <int NTI, int TO>
 SD_INLINE void dense_safe(const f32x4 (&in)[NTI], f32x4 (&out)[TO], const float* w, const float* bias_scaled, float inv, int lane) {
   const int g = lane >> 4;
-  constexpr int KB = (NTI + 1) / 2;
   const float sg = row_downscale<NTI>(in), rs = 1.0f / sg;  // powers of two: exact
   // one output tile at a time (the input is split again for each): this path is cold, what matters is that it adds no register pressure
   // to the step loop it sits in (the three-waves-per-SIMD instantiations have 168 registers)
 #pragma unroll
   for (int to = 0; to < TO; ++to) {
     f32x4 o1[1] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
-    dense<NTI, 1, true>(in, o1, w + to * KB * 512, lane, sg);
+    dense<NTI, 1, true>(in, o1, w + to * sd_image_floats(1, NTI), lane, sg);
     const f32x4 b = load_tile4(bias_scaled, to, g);
 #pragma unroll
     for (int r = 0; r < 4; ++r) out[to][r] = __builtin_fmaf(o1[0][r], rs, b[r]) * inv;
@@ -454,7 +451,7 @@ SD_INLINE void mlp_out_tiles(const HidSplit& hs, const float* lds, const float* 
     u[o] = load_tile4(bias + 192, t0 + o, g);  // b_out (times the layer's scale)
     mx[o] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   }
-  dense_pre<2, OT>(hs.h, hs.l, u, mx, reinterpret_cast<const f16x8*>(lds + sd_off_wout(NT) + t0 * 2 * 512), lane);
+  dense_pre<2, OT>(hs.h, hs.l, u, mx, reinterpret_cast<const f16x8*>(lds + sd_off_wout(NT) + t0 * sd_image_floats(1, SD_HT)), lane);
   fold_lo<OT>(u, mx);
   unscale_tiles<OT>(u, inv_out);
 }
@@ -466,7 +463,7 @@ SD_INLINE void mlp_out_tiles_safe(const HidSplit& hs, float rs, const float* lds
   f32x4 mx[OT];
 #pragma unroll
   for (int o = 0; o < OT; ++o) u[o] = mx[o] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  dense_pre<2, OT>(hs.h, hs.l, u, mx, reinterpret_cast<const f16x8*>(lds + sd_off_wout(NT) + t0 * 2 * 512), lane);
+  dense_pre<2, OT>(hs.h, hs.l, u, mx, reinterpret_cast<const f16x8*>(lds + sd_off_wout(NT) + t0 * sd_image_floats(1, SD_HT)), lane);
   fold_lo<OT>(u, mx);
 #pragma unroll
   for (int o = 0; o < OT; ++o) {
@@ -985,11 +982,11 @@ SD_INLINE void store_rows(float* __restrict__ dst, float* __restrict__ trash, ui
 // augmented design matrix Xa = [X | 1] (the ones column carries the intercept, logistic_regression.py:52-55):
 //   logits image: blocks [row tile][feature K-block]   (out = data rows, sum over features)      logits = Xa w
 //   grad   image: blocks [feature tile][row K-block]    (out = features,  sum over data rows)     grad   = Xa^T r
-// both in the (to, kb, part, lane, 8 halves) layout of k_pack_mlp; data rows are padded with zero rows.
+// both in the format of image_format.hpp; data rows are padded with zero rows.
 __host__ __device__ inline int sd_lr_row_tiles(int n) { return (n + 15) / 16; }
 __host__ __device__ inline int sd_lr_row_kb(int n) { return (n + 31) / 32; }
-__host__ __device__ inline int sd_lr_logit_floats(int NT, int n) { return sd_lr_row_tiles(n) * sd_kb(NT) * 512; }
-__host__ __device__ inline int sd_lr_grad_floats(int NT, int n) { return NT * sd_lr_row_kb(n) * 512; }
+__host__ __device__ inline int sd_lr_logit_floats(int NT, int n) { return sd_image_floats(sd_lr_row_tiles(n), NT); }
+__host__ __device__ inline int sd_lr_grad_floats(int NT, int n) { return sd_blocks_floats(NT, sd_lr_row_kb(n)); }
 __host__ __device__ inline int sd_lr_floats(int NT, int n) { return sd_lr_logit_floats(NT, n) + sd_lr_grad_floats(NT, n); }
 
 // Per-datum factor of the logistic-regression score.  The reference differentiates

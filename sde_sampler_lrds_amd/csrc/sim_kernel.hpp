@@ -193,9 +193,9 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
   const int share = (REF == RF_GMM_BIG || REF == RF_GMM_FULL || REF == RF_GMM_MM) ? __builtin_amdgcn_readfirstlane(a.ref_share) : 0;
   float* sh_tab = lds + sd_lds_weight_floats(NT);
   const int sh_floats = sd_share_buf_floats(share);
-  // full-covariance mixtures: a component's precision image (NT*KB*512 floats) is staged in FULL_PP pieces of FULL_TO output
+  // full-covariance mixtures: a component's precision image (sd_image_floats(NT, NT)) is staged in FULL_PP pieces of FULL_TO output
   // tiles each (32 KiB at d = 128), piece after piece through the same two buffers
-  constexpr int FULL_PP = NT > 4 ? 2 : 1, FULL_TO = NT / FULL_PP, FULL_PIECE = FULL_TO * ((NT + 1) / 2) * 512;
+  constexpr int FULL_PP = sd_full_pieces(NT), FULL_TO = NT / FULL_PP, FULL_PIECE = sd_full_piece_floats(NT);
   static_assert(REF != RF_GMM_FULL || NT % FULL_PP == 0, "pieces hold whole output tiles");
   const int p = lane & 15, g = lane >> 4;
   constexpr bool lin = FORM == SDENG_FORM_LIN;
@@ -237,7 +237,7 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
     }
     if constexpr (REF == RF_GMM_MM) {  // always workgroup-shared: piece 0 = the logit image of step 0
       __syncthreads();
-      if (a.N > 0) dma_table_shared(a.ref_tab, sh_tab, a.ref_kc * ((NT + 1) / 2) * 512, share, wave, lane);
+      if (a.N > 0) dma_table_shared(a.ref_tab, sh_tab, sd_mm_logit_floats(a.ref_kc, NT), share, wave, lane);
     }
     if constexpr (REF == RF_GMM_FULL) {  // always workgroup-shared: piece 0 of the first precision image
       __syncthreads();
@@ -380,7 +380,7 @@ __global__ void __launch_bounds__((64 * sd_waves_of<NT, REF, SC, FORM, PAR>()), 
         const int kt = a.ref_kc, kbk = (kt + 1) / 2;       // live component tiles, K-blocks of the mean product
         const float* cs = a.ref_mean + static_cast<size_t>(k) * 2 * dpad;  // [centre][1/var] of this step
         const float* bk = a.ref_consts + static_cast<size_t>(k) * (KTM * 16);
-        const int logit_floats = kt * KBX * 512, mean_floats = NT * kbk * 512;
+        const int logit_floats = sd_mm_logit_floats(kt, NT), mean_floats = sd_mm_mean_floats(kt, NT);
         const float* img = a.ref_tab + static_cast<size_t>(k) * (logit_floats + mean_floats);
         f16x8 ch[KBX], cl[KBX];
         {

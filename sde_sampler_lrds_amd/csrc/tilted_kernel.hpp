@@ -26,7 +26,7 @@
 #define TL_H 128            // channels of the EBM's net
 #define TL_HT 8             // channel tiles
 #define TL_KBH 4            // 32-channel K-blocks
-#define TL_SLOT 16384       // floats of one image slot (8 x 4 blocks of 512): 64 KiB
+#define TL_SLOT sd_image_floats(TL_HT, TL_HT)  // floats of one image slot (a [128 x 128] image): 64 KiB
 #define TL_KMAX 16
 // image slots: forward net, transposed net, then per mixture component P^T and P
 enum { TL_TE1S = 0, TL_TE1C, TL_TE2, TL_WIN, TL_WH, TL_WOUT = TL_WH + 4, TL_WOUT_T, TL_WH_T, TL_WIN_T = TL_WH_T + 4, TL_EIG, TL_NIMG = TL_EIG + 2 * TL_KMAX };
@@ -59,19 +59,11 @@ struct TiltedRows {
   float* dv;            // [M, d] f_r xs, the cotangent of v
 };
 
-// one matrix (or a column range of it) -> one image slot, its power-of-two scale (k_weight_scales' rule) and its scaled bias
-struct TiltedPackJob {
-  const float* src;     // [n_out, ld] row-major (transpose: [n_in, ld], the image is of src^T)
-  const float* scale_src;  // the matrix whose largest entry decides the scale ([scale_n] floats)
-  const float* bias;    // [n_out] or nullptr
-  int n_out, n_in, ld, col0, transpose, scale_n, slot, bias_off;  // bias_off: TL_C_* of the bias, -1: none
-};
-struct TiltedPackArgs {
-  float* pack;
+// the constants block: time-embedding frequencies, the Gaussian of the input scaling and the mixture prior, padded (k_tilted_consts)
+struct TiltedConstArgs {
   float* consts;
   const float *coeff, *phase, *mean_gauss, *var_gauss, *weights, *means, *vars;
-  int d, K, njobs;
-  TiltedPackJob job[TL_NIMG];
+  int d, K;
 };
 // Langevin moves over the tilted density (k_tilted_moves, tilted_moves_inst.hip): the chain state next to the TiltedArgs of the net.
 // The caller's x / grad hold the current state and are updated in place on acceptance; prop / gprop are the proposal and the score at it.
@@ -89,7 +81,7 @@ struct TiltedMovesArgs {
   uint32_t seed_lo, seed_hi;
   long long chain0;
 };
-int sd_launch_tilted_pack(const TiltedPackArgs& a, hipStream_t s);
+int sd_launch_tilted_consts(const TiltedConstArgs& a, hipStream_t s);
 int sd_launch_tilted_moves(const TiltedArgs& a, const TiltedMovesArgs& mv, int NT, int grid, int waves, hipStream_t s);
 int sd_launch_tilted(const TiltedArgs& a, int NT, int grid, int waves, hipStream_t s);
 int sd_launch_tilted_train(const TiltedArgs& a, const TiltedRows& rows, int NT, int grid, int waves, hipStream_t s);

@@ -9,7 +9,7 @@ struct TiltedRdsArgs {
   unsigned flags;         // SDENG_FLAG_ITO
   int N;
   const float* coef;      // [N][SDENG_NCOEF]
-  const float* wpack;     // packed drift-net image (k_pack_mlp), biases and layer scales behind it
+  const float* wpack;     // packed drift-net image (sim_common.hpp), biases and layer scales behind it
   const float* temb;      // [N][64] time embedding of the drift net, per step
   const float* te_tab;    // [N][128] the EBM's time embedding per step: (b_in + e) 2^e_in, the accumulator its input layer starts from
   float clip_model;

@@ -8,7 +8,7 @@
 //      walk of its own, the score is sdeng_tilted_eval's at the same row, bit for bit.  Every row of a step shares the step's time, so the
 //      EBM's time embedding is a per-step quantity: a table [N][128] made once per launch by k_tilted_rds_times through tl_time_embed
 //      (three stagings fewer per step), read back in the lane's register order as the accumulator of the input layer;
-//   b. the control u = clip(FourierMLP_4x64(t_k, x_k)): mlp_hidden_scaled and the output tiles of sim_device.hpp over the image k_pack_mlp
+//   b. the control u = clip(FourierMLP_4x64(t_k, x_k)): mlp_hidden_scaled and the output tiles of sim_device.hpp over the image k_pack_images
 //      makes, staged through the same buffer -- input and hidden layers, then (d > 64, where the image is 96 KiB) the output layer;
 //   c. the noise of Philox stream 0 in the step loop's counter layout, or the caller's;
 //   d. update and running cost in the statement order of k_simulate's tail (sim_kernel.hpp).
@@ -25,9 +25,9 @@ SD_INLINE uint32_t tlm_fresh(uint32_t v) {
 
 // 2 KiB blocks of the drift-net image (sim_common.hpp): input and hidden layers, then the output layer.  The whole image fits the 64 KiB
 // buffer up to four feature tiles (32 blocks at NT = 4); above, the two pieces are staged one after the other (32 + 16 blocks at NT = 8).
-constexpr int tlr_hidden_blocks(int NT) { return 4 * ((NT + 1) / 2) + 16; }
-constexpr int tlr_out_blocks(int NT) { return 2 * NT; }
-constexpr bool tlr_one_image(int NT) { return (tlr_hidden_blocks(NT) + tlr_out_blocks(NT)) * 512 <= TL_SLOT; }
+constexpr int tlr_hidden_blocks(int NT) { return sd_off_wout(NT) / SD_BLOCK_FLOATS; }
+constexpr int tlr_out_blocks(int NT) { return sd_image_blocks(NT, SD_HT); }
+constexpr bool tlr_one_image(int NT) { return sd_lds_weight_floats(NT) <= TL_SLOT; }
 
 // mlp_out_tiles (sim_device.hpp) with the output layer's blocks at `wout`: behind the hidden layers of a whole image, or at the head of the
 // buffer when the layer is staged alone
@@ -40,7 +40,7 @@ SD_INLINE void tlr_out_tiles(const HidSplit& hs, const float* wout, const float*
     u[o] = load_tile4(bias + 192, t0 + o, g);  // b_out (times the layer's scale)
     mx[o] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   }
-  dense_pre<2, OT>(hs.h, hs.l, u, mx, reinterpret_cast<const f16x8*>(wout + t0 * 2 * 512), lane);
+  dense_pre<2, OT>(hs.h, hs.l, u, mx, reinterpret_cast<const f16x8*>(wout + t0 * sd_image_floats(1, SD_HT)), lane);
   fold_lo<OT>(u, mx);
   unscale_tiles<OT>(u, inv_out);
 }
@@ -48,7 +48,7 @@ SD_INLINE void tlr_out_tiles(const HidSplit& hs, const float* wout, const float*
 template <int NT>
 __global__ void __launch_bounds__(512, 2) k_tilted_rds(const TiltedArgs a, const TiltedRdsArgs rn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  static_assert(tlr_hidden_blocks(NT) * 512 <= TL_SLOT && tlr_out_blocks(NT) * 512 <= TL_SLOT, "each staged piece of the drift net fits the image buffer");
+  static_assert(sd_off_wout(NT) <= TL_SLOT && sd_image_floats(NT, SD_HT) <= TL_SLOT, "each staged piece of the drift net fits the image buffer");
   const int tid = threadIdx.x, lane0 = tid & 63, threads = blockDim.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = threads >> 6;
   const int p = lane0 & 15, g0 = lane0 >> 4;
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(512, 2) k_tilted_rds(const TiltedArgs a, const
   const bool lin = rn.form == SDENG_FORM_LIN;
   const float* bias = rn.wpack + sd_off_bias(NT);
   constexpr bool one_image = tlr_one_image(NT);
-  const float* wout = one_image ? lds + tlr_hidden_blocks(NT) * 512 : lds;
+  const float* wout = one_image ? lds + sd_off_wout(NT) : lds;
 
   for (int round = 0; round < rounds; ++round) {
     const int tile = (round * gridDim.x + blockIdx.x) * nw + wave;
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(512, 2) k_tilted_rds(const TiltedArgs a, const
         mlp_hidden_scaled<NT>(x, hid, lds, bias, rn.temb + static_cast<size_t>(k) * SD_H, lane, ns);
         hs = split_hidden(hid);
       }
-      if (!one_image) tl_stage(lds, rn.wpack + tlr_hidden_blocks(NT) * 512, tlr_out_blocks(NT), tid, threads);
+      if (!one_image) tl_stage(lds, rn.wpack + sd_off_wout(NT), tlr_out_blocks(NT), tid, threads);
 
       // ---- c., d. per pair of output tiles: out_layer -> clip -> cost -> noise -> integrator -> Ito term (k_simulate's tail) ----
       if (active) {

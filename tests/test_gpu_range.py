@@ -3,7 +3,7 @@
 path fp32's range, both held to the oracle here:
 
 * weights: each matrix is stored times a power of two that brings its largest entry to [1, 2) when that entry is below 2^-10 or at /
-  above 2^14 (k_weight_scales), the layer's output is multiplied back -- the reference's OWN default initialisation puts the last
+  above 2^14 (image_format.hpp), the layer's output is multiplied back -- the reference's OWN default initialisation puts the last
   layer at |w| <= 1.25e-7 (models/utils.py:7-22 kaiming_uniform_zeros_), f16-subnormal: before this the control at init carried a
   1.3e-4 relative error, now fp32 round-off;
 * states / activations: an operand beyond 65 504 is detected after the fact (one compare per tile-step) and the step's net is
