@@ -27,6 +27,7 @@ import torch
 
 from .. import _lib as L
 from .. import engine as E
+from .. import parallel
 from .. import routes as R
 from ..utils.common import Results, make_results
 from . import training as T
@@ -89,6 +90,8 @@ class BaseOCLoss:
     def compute_loss(self, rnd, samples=None):
         mask = self.filter(rnd, samples=samples)
         assert mask.shape == rnd.shape
+        if parallel.is_sharded(self.dist):
+            return self._compute_loss_global(rnd, mask)
         if self.method == "lv_traj":
             rnd = rnd.reshape(self.traj_per_sample, -1, 1)
             mask = mask.reshape(self.traj_per_sample, -1, 1).all(dim=0)
@@ -97,6 +100,36 @@ class BaseOCLoss:
         else:
             self.n_filtered += (mask.numel() - mask.sum()).item()
             loss = rnd[mask].var() if self.method == "lv" else rnd[mask].mean()
+        return loss, {"train/n_filtered_cumulative": self.n_filtered}
+
+    def _compute_loss_global(self, rnd, mask):
+        """``compute_loss`` of a sharded run (``self.dist``: a process group of more than one rank): ``rnd`` is this rank's shard, the value
+        the objective over ALL ranks' particles -- the same bits on every rank -- from ONE 32-byte all-gather (``parallel.global_moments``:
+        per-shard (n, mean, M2) in float64 on the device, combined with Chan's update).  It enters autograd as value.detach() + (local -
+        local.detach()), ``local`` being this shard's terms of the global expression with the global mean and count as constants: each
+        rank's gradient is its exact partial sum of the global one (for 'lv' because sum_i (rnd_i - mean) = 0 over the global batch), so
+        ``parallel.all_reduce_grads`` with SUM completes it.  'lv_traj': the variance over a sample's trajectories stays local (they live on
+        one rank), the mean runs over the global count of kept samples.  An empty shard is legal; n <= 1 gives NaN, as ``torch.var`` does."""
+        tps = 1
+        if self.method == "lv_traj":
+            tps = self.traj_per_sample
+            rnd = rnd.reshape(tps, -1, 1)
+            mask = mask.reshape(tps, -1, 1).all(dim=0)
+            kept = rnd[:, mask].double().var(dim=0)  # [kept samples of this shard]
+            with torch.no_grad():
+                per_sample = torch.zeros(mask.shape, dtype=torch.float64, device=rnd.device)
+                per_sample[mask] = kept
+            mom = parallel.global_moments(per_sample, mask, self.dist)
+            value, local = parallel.kept_mean(mom), kept.sum() / mom[parallel.M_N]
+        else:
+            mom = parallel.global_moments(rnd, mask, self.dist)
+            if self.method == "lv":
+                value = parallel.unbiased_var(mom)
+                local = ((rnd[mask].double() - mom[parallel.M_MEAN]) ** 2).sum() / (mom[parallel.M_N] - 1)
+            else:
+                value, local = parallel.kept_mean(mom), rnd[mask].double().sum() / mom[parallel.M_N]
+        self.n_filtered += tps * int(mom[parallel.M_ROWS] - mom[parallel.M_N])
+        loss = (value.detach() + (local - local.detach())).to(rnd.dtype)
         return loss, {"train/n_filtered_cumulative": self.n_filtered}
 
     @staticmethod
@@ -111,7 +144,7 @@ class BaseOCLoss:
                 w, res = parallel.global_weights(rnd, dist)
             else:
                 w, res = None, parallel.global_results(rnd, dist)
-            metrics = {"eval/elbo": res["elbo"]}
+            metrics = {"eval/elbo": res["elbo"], "eval/n_particles": res["n"]}  # (the count over all ranks: what the estimators are over)
             preds = {}
             if compute_weights:
                 preds["log_norm_const_is"] = res["log_norm_const_is"]

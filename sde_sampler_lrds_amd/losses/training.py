@@ -7,6 +7,7 @@ import torch
 
 from .. import _lib as L
 from .. import engine as E
+from .. import parallel
 from .. import routes as R
 
 
@@ -153,9 +154,16 @@ def rollout(loss, ts, x, simulate=None, perturb=None):
 
 
 def kl_weights(loss, rnd_val, x_n):
-    """KL value of the particles that pass ``loss.filter`` and its cotangent: -> (mask, w = d mean(rnd[mask]) / d rnd_b, value)."""
+    """KL value of the particles that pass ``loss.filter`` and its cotangent: -> (mask, w = d mean(rnd[mask]) / d rnd_b, value).  A sharded run
+    (``loss.dist``: a process group of more than one rank): the mean is over ALL ranks' kept particles (``parallel.global_moments``, one 32-byte
+    all-gather), so w divides by the global count and every adjoint downstream yields this rank's exact partial sum of the global gradient."""
     mask = loss.filter(rnd_val, samples=x_n)
     assert mask.shape == rnd_val.shape
+    if parallel.is_sharded(loss.dist):
+        mom = parallel.global_moments(rnd_val, mask, loss.dist)
+        n = mom[parallel.M_N]
+        loss.n_filtered += int(mom[parallel.M_ROWS] - n)
+        return mask, mask.to(rnd_val.dtype) / n.to(rnd_val.dtype), parallel.kept_mean(mom).to(rnd_val.dtype)
     loss.n_filtered += (mask.numel() - mask.sum()).item()
     w = mask.to(rnd_val.dtype) / mask.sum()
     return mask, w, rnd_val[mask].mean()

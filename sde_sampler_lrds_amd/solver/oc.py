@@ -22,6 +22,7 @@ from ..losses import oc as losses
 from ..models.mlp import FourierMLP, TimeEmbed
 from ..models.reparam import CancelDriftCtrl, ClippedCtrl, LerpCtrl, ScoreCtrl
 from ..models import utils as mutils
+from .. import parallel
 from .. import routes as R
 from ..reference import EnergyReference, MarginalReference
 from ..routes import UnsupportedByEngine
@@ -80,6 +81,7 @@ class TrainableDiff:
         self.eval_sample_losses = None
         self.eval_marginal_dims = list(cfg.get("eval_marginal_dims", []))
         self.seed = cfg.get("seed", 1)
+        self.dist = None  # torch.distributed of a sharded run (set_distributed)
         torch.manual_seed(self.seed)
         self.setup_models()
         self.to(self.device)
@@ -121,7 +123,37 @@ class TrainableDiff:
         loss.seed = self.seed
         loss.graph_training = bool(self.cfg.get("graph_training", False))  # log-variance training: batched control pass as a hipGraph (works; measured no gain: the step is bound by its read-backs, tools/probe_train_host.py)
         loss.split_tiles = bool(self.cfg.get("split_tiles", True))  # evaluation batches of a few thousand particles: low-latency kernels
+        loss.dist = self.dist  # (a loss rebuilt after set_distributed, CMCD.update_prior, stays sharded)
         return loss
+
+    # -- sharded runs ------------------------------------------------------------------------
+    def set_distributed(self, dist):
+        """Train and evaluate across the ranks of ``dist`` (an initialised torch.distributed module, RCCL or gloo; one process per rank,
+        every rank built from the same cfg and seed).  ``compute_loss`` / ``compute_results`` then draw the GLOBAL batch as before -- torch's
+        generators stay in lockstep with a single-process run -- and keep rows ``parallel.shard_bounds(B, world, rank)``, with
+        ``loss.particle0`` at the shard's first row, so every particle has the noise (and engine-drawn x0) it has in a single-process run;
+        the loss value is the objective over all ranks' particles and ``step()`` sums the gradients (``parallel.all_reduce_grads``), so every
+        rank takes the same optimiser step.  ``traj_per_sample > 1``: the repeats of a shard's samples are keyed ``traj_per_sample * lo +
+        row`` -- distinct across the ranks, but not the keys the single-process run gives those trajectories (there repeat j of sample i is
+        row j * B + i).  ``Results.samples`` / ``weights`` are this rank's shard; the metrics are global.  ``None`` (or a group of one rank)
+        is the single-process path."""
+        self.dist = dist
+        self.loss.dist = dist
+
+    def _shard(self, total):
+        """This rank's rows [lo, hi) of a global batch of ``total``, or None for a single-process run."""
+        if not parallel.is_sharded(self.dist):
+            return None
+        return parallel.shard_bounds(total, self.dist.get_world_size(), self.dist.get_rank())
+
+    def _on_shard(self, lo, fn):
+        """``fn()`` with ``loss.particle0`` moved to global row ``lo``; restored whatever happens."""
+        keep = self.loss.particle0
+        self.loss.particle0 = keep + lo
+        try:
+            return fn()
+        finally:
+            self.loss.particle0 = keep
 
     def modules(self):
         return [m for m in (self.target, self.prior, self.sde, self.generative_ctrl, getattr(self, "generative_ctrl_ema", None),
@@ -157,6 +189,15 @@ class TrainableDiff:
         if self.eval_ts is None:
             self.eval_ts = self.eval_timesteps(device=self.device) if self._plain_grid() else self.eval_timesteps().to(self.device)
         ts = self.eval_ts
+        span = self._shard(self.eval_batch_size)
+        if span is not None:  # a sharded run: this rank's rows of the same batch (an engine-drawn x0 is keyed by the global row; a tensor is sliced)
+            from .. import engine as E
+            lo, hi = span
+            x = E.InitialDraw(self.prior, hi - lo, self.device) if isinstance(x, E.InitialDraw) else x[lo:hi].clone()
+            return self._on_shard(lo, lambda: self._results_passes(ts, x, use_ema))
+        return self._results_passes(ts, x, use_ema)
+
+    def _results_passes(self, ts, x, use_ema):
         results = self._compute_results(ts, x, use_ema=use_ema, compute_weights=True)
         assert results.xs.shape == (len(ts), *results.samples.shape)
         torch.cuda.synchronize(self.device)
@@ -219,6 +260,10 @@ class TrainableDiff:
         x = self.prior.sample((self.train_batch_size,)).to(self.device)
         if self.train_ts is None:
             self.train_ts = self.train_timesteps(device=self.device) if self._plain_grid() else self.train_timesteps().to(self.device)
+        span = self._shard(self.train_batch_size)
+        if span is not None:  # a sharded run: the global batch was drawn (generators in lockstep with a single process), this rank keeps its rows
+            lo, hi = span
+            return self._on_shard(self.loss.traj_per_sample * lo, lambda: self._compute_loss(self.train_ts, x[lo:hi].clone()))  # (a copy: its own, aligned storage)
         return self._compute_loss(self.train_ts, x)
 
     def _compute_loss(self, ts, x):
@@ -237,6 +282,8 @@ class TrainableDiff:
             loss = self.scale_loss * loss
         loss.backward()
         params = self.trainable_parameters()
+        if self.dist is not None:  # a sharded run: the value is global already, the gradients are per-rank partial sums -- one SUM all-reduce
+            parallel.all_reduce_grads(params, self.dist)
         loss_ok = bool(loss.isfinite()) if self.max_loss is None else bool(loss.abs() <= self.max_loss)
         # one read-back for all parameters (a per-parameter bool() costs a stream synchronisation each): max |grad| is NaN / inf
         # exactly when some gradient entry is (solver/base.py:425-433 checks every parameter)
