@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+import dataclasses
 import math
 import weakref
 
@@ -525,8 +526,35 @@ def require_gpu(x: torch.Tensor):
                            "(no CPU implementation is shipped)")
 
 
+def new_desc() -> L.Desc:
+    """A fresh sdeng_desc with the ABI version set: the one place it is stamped."""
+    return L.Desc(abi_version=L.ABI_VERSION)
+
+
+@dataclasses.dataclass
+class Launched:
+    """What a step-loop launch ran on, for the gradient code of the same training call: the loss's declaration of the loop (``decl``, losses/oc.py
+    StepLoop), the device table ``coef`` and the compiled parts an adjoint shares with it -- the control's ``net``, the reference drift ``ref``,
+    the control's lerp ``prior`` (never a launch's initial density) and, for CMCD, its ``target`` without the terminal clip -- with the tensors
+    ``keep`` holds alive for them."""
+    coef: torch.Tensor
+    net: L.Net
+    prior: L.Dist
+    ref: L.Ref = None
+    target: L.Dist = None
+    decl: object = None
+    keep: list = dataclasses.field(default_factory=list)
+
+
+def compile_ctrl(ctrl, coef, device, ref=("none", {}), decl=None) -> Launched:
+    """The shared compile step: control, its lerp prior, reference drift and coefficient table as the kernels read them."""
+    keep = []
+    return Launched(_f32c(coef.to(device=device)), net_desc(ctrl, device, keep), dist_desc(ctrl_target(ctrl)[1], device, keep),
+                    ref_desc(ref[0], ref[1], device, keep), decl=decl, keep=keep)
+
+
 def run(desc: L.Desc, x: torch.Tensor, keep: list, return_traj=False, noise=None, events=None):
-    """Fill the I/O pointers of ``desc`` and launch.  Returns (x_N [B,d], rnd [B,1], xs or None)."""
+    """Fill the I/O pointers of ``desc`` (from ``new_desc``) and launch.  Returns (x_N [B,d], rnd [B,1], xs or None)."""
     require_gpu(x)
     lib = L.lib()
     device = x.device
@@ -542,7 +570,6 @@ def run(desc: L.Desc, x: torch.Tensor, keep: list, return_traj=False, noise=None
         x_out = torch.empty_like(xin)
     rnd = torch.empty(B, 1, dtype=torch.float32, device=device)
     xs = torch.empty(N + 1, B, d, dtype=torch.float32, device=device) if return_traj else None
-    desc.abi_version = L.ABI_VERSION
     desc.B, desc.d = B, d
     desc.x_out, desc.rnd_out = x_out.data_ptr(), rnd.data_ptr()
     desc.xs_out = xs.data_ptr() if return_traj else None
@@ -575,7 +602,7 @@ def euler_states(sde, timesteps: torch.Tensor, x: torch.Tensor, increments=None,
     device, keep = x.device, []
     ts = timesteps.detach().to("cpu", torch.float32)
     N = ts.numel() - 1
-    desc = L.Desc()
+    desc = new_desc()
     desc.form, desc.flags, desc.N = L.FORM_EM, 0, N
     desc.seed, desc.particle0 = int(seed), int(particle0)
     coef = torch.zeros(N, L.NCOEF, dtype=torch.float32)
@@ -801,8 +828,7 @@ def rwmh_moves(target, x, lp, step, n_moves, *, keep_from=0, target_acceptance=0
 def _net_only_desc(ctrl, t_unique: torch.Tensor, n_times: int, d: int, device, keep: list, who="ctrl_vjp", own_workspace=False):
     """The descriptor sdeng_ctrl_vjp reads -- the drift net of a ClippedCtrl, a coefficient table that holds only the ``n_times`` times (column 0),
     the shared workspace or one of its ``own`` (its weight images then survive other engine calls) -> (desc, coef, workspace), for the caller to keep alive."""
-    desc = L.Desc()
-    desc.abi_version = L.ABI_VERSION
+    desc = new_desc()
     desc.net = net_desc(ctrl, device, keep)
     if desc.net.ctrl_kind != L.CTRL_CLIPPED:
         raise UnsupportedByEngine(f"{who}: ClippedCtrl only")
@@ -891,36 +917,36 @@ class VjpSession:
         return self.rows.result()
 
 
-def kl_adjoint(ctrl, coef: torch.Tensor, xs: torch.Tensor, z, w: torch.Tensor, lam_n: torch.Tensor, *, lin: bool, ito: bool, ref=("none", {})):
+def kl_adjoint(ctrl, coef: torch.Tensor, xs: torch.Tensor, z, w: torch.Tensor, lam_n: torch.Tensor, *, lin: bool, ito: bool, ref=("none", {}), parts=None):
     """sdeng_kl_adjoint: the whole adjoint recursion of KL training in one launch (ClippedCtrl, or ScoreCtrl on a diagonal mixture target; no
     reference, or a diagonal Gaussian / mixture reference).  ``coef`` [N,16] on the device, ``xs`` [N,B,d] = x_0 .. x_{N-1}, ``z`` [N,B,d]
-    the trajectory's normals (or None), ``w`` [B,1] = d loss / d rnd, ``lam_n`` [B,d] = lambda_N.  Returns (per-row arrays as ``ctrl_vjp``
+    the trajectory's normals (or None), ``w`` [B,1] = d loss / d rnd, ``lam_n`` [B,d] = lambda_N.  ``parts``: the ``Launched`` record of the step
+    loop this is the adjoint of -- its net, lerp prior, reference and table as compiled (``coef`` must then be ``parts.coef`` itself and ``ref`` is the
+    record's).  The control's own target is compiled here: the step loop's slot holds the terminal target.  Returns (per-row arrays as ``ctrl_vjp``
     -- plus ``dst`` [N,B], the per-particle cotangent of s_theta(t_k), for a ScoreCtrl --, lambda_0)."""
     require_gpu(xs)
     lib = L.lib()
     device, keep = xs.device, []
     N, B, d = xs.shape
-    desc = L.Desc()
-    desc.abi_version = L.ABI_VERSION
+    if parts is not None and coef is not parts.coef:
+        raise ValueError("kl_adjoint: with parts, coef must be the table of that launch (parts.coef)")
+    parts = parts or compile_ctrl(ctrl, coef, device, ref)
+    desc = new_desc()
     desc.form = L.FORM_LIN if lin else L.FORM_EM
     desc.flags = L.FLAG_ITO if ito else 0
     desc.B, desc.d, desc.N = B, d, N
-    desc.net = net_desc(ctrl, device, keep)
+    desc.net, desc.prior, desc.ref, desc.coef = parts.net, parts.prior, parts.ref, parts.coef.data_ptr()
     if not adjoint_ctrl_ok(ctrl):
         raise UnsupportedByEngine("kl_adjoint: ClippedCtrl, or ScoreCtrl on a diagonal mixture target")
     score = desc.net.ctrl_kind != L.CTRL_CLIPPED
     ext_score = None
-    tgt, lerp_prior = ctrl_target(ctrl)  # (None, None) for a ClippedCtrl: SDENG_DIST_NONE descriptors
+    tgt = ctrl_target(ctrl)[0]  # None for a ClippedCtrl: a SDENG_DIST_NONE descriptor
     if R.dist_kind(tgt) in R.GRAPHLESS_TARGETS:
         _, ext_score = dist_eval(tgt, xs.reshape(N * B, d), want_logp=False, want_score=True)
     else:
         desc.target = dist_desc(tgt, device, keep)
-    desc.prior = dist_desc(lerp_prior, device, keep)
-    desc.ref = ref_desc(ref[0], ref[1], device, keep)
     if desc.ref.kind not in (L.REF_NONE, L.REF_GAUSS_DIAG, L.REF_GMM_DIAG):
         raise UnsupportedByEngine("kl_adjoint: diagonal references only")
-    cf = _f32c(coef.to(device=device))
-    desc.coef = cf.data_ptr()
     rows = _RowArrays(_f32c(xs).view(N * B, d))
     lam0 = torch.empty(B, d, dtype=torch.float32, device=device)
     wv, ln = _f32c(w).view(B), _f32c(lam_n)
@@ -951,11 +977,32 @@ def ctrl_forward_rows(ctrl, t_unique: torch.Tensor, xs: torch.Tensor) -> torch.T
     return u.view(M, B, d)
 
 
-def cmcd_kl_adjoint(ctrl, sde, coef: torch.Tensor, xs: torch.Tensor, cbar: torch.Tensor, w: torch.Tensor, lam_n: torch.Tensor, score_ext=None):
+def cmcd_desc(ctrl, sde, coef, device, form=L.FORM_CMCD, parts=None, decl=None):
+    """CMCD's descriptor without its sizes, flags and I/O, for the step loop, the EUBO loop and the adjoint alike -> (desc, ``parts``).  Compiled
+    here unless ``parts`` (an earlier launch's record) is given: control, target, prior (``Launched.target``: no clip -- a forward launch adds
+    the terminal clip to its own copy)."""
+    if parts is None:
+        keep = []
+        net = net_desc(ctrl, device, keep)
+        target, prior = _self_of(sde.target_score), _self_of(sde.prior_score)
+        if target is None or prior is None:
+            raise UnsupportedByEngine("ControlledLangevinSDE.target_score / prior_score must be bound Distribution.score methods")
+        parts = Launched(_f32c(coef.to(device=device)), net, dist_desc(prior, device, keep), target=dist_desc(target, device, keep), decl=decl, keep=keep)
+    desc = new_desc()
+    desc.form = form
+    desc.net, desc.target, desc.prior, desc.coef = parts.net, parts.target, parts.prior, parts.coef.data_ptr()
+    desc.cmcd_g = scalar_of(sde.diff_coeff)
+    desc.cmcd_clip = scalar_of(sde.clip_score) if sde.clip_score else 0.0
+    return desc, parts
+
+
+def cmcd_kl_adjoint(ctrl, sde, coef: torch.Tensor, xs: torch.Tensor, cbar: torch.Tensor, w: torch.Tensor, lam_n: torch.Tensor, score_ext=None, parts=None):
     """sdeng_cmcd_kl_adjoint: the adjoint of CMCD's KL training over the N + 1 evaluation points in one launch.  ``coef`` [N+1,16] the CMCD
     table of the step loop (device), ``xs`` [N+1,B,d] = x_0 .. x_N, ``cbar`` [N,B,d] = cost_j dt_j + db_j, ``w`` [B,1] = d loss / d rnd,
     ``lam_n`` [B,d] = d (sum w (-log pi~(x_N))) / d x_N.  ``score_ext`` [(N+1)*B,d]: the target score of every row for a graph-less target
-    (evaluated here when not given).  Returns (per-row arrays as ``kl_adjoint`` over the (N+1)*B rows, Lambda_0)."""
+    (evaluated here when not given).  ``parts``: the ``Launched`` record of the step loop this is the adjoint of (``coef`` must then be
+    ``parts.coef`` itself; compiled here otherwise).
+    Returns (per-row arrays as ``kl_adjoint`` over the (N+1)*B rows, Lambda_0)."""
     require_gpu(xs)
     if xs.dim() != 3 or cbar.dim() != 3:
         raise ValueError(f"cmcd_kl_adjoint: xs [N+1,B,d] and cbar [N,B,d] expected, got {tuple(xs.shape)} and {tuple(cbar.shape)}")
@@ -965,28 +1012,18 @@ def cmcd_kl_adjoint(ctrl, sde, coef: torch.Tensor, xs: torch.Tensor, cbar: torch
         raise ValueError(f"cmcd_kl_adjoint: shapes disagree: xs {tuple(xs.shape)}, cbar {tuple(cbar.shape)} (want {(N, B, d)}), w {tuple(w.shape)} "
                          f"(want {B} entries), lam_n {tuple(lam_n.shape)} (want {(B, d)}), coef {tuple(coef.shape)} (want {(M, L.NCOEF)})")
     lib = L.lib()
-    device, keep = xs.device, []
-    desc = L.Desc()
-    desc.abi_version = L.ABI_VERSION
-    desc.form = L.FORM_CMCD
+    device = xs.device
+    if parts is not None and coef is not parts.coef:
+        raise ValueError("cmcd_kl_adjoint: with parts, coef must be the table of that launch (parts.coef)")
+    desc, parts = cmcd_desc(ctrl, sde, coef, device, parts=parts)
     desc.B, desc.d, desc.N = B, d, N
-    desc.net = net_desc(ctrl, device, keep)
-    target, prior = _self_of(sde.target_score), _self_of(sde.prior_score)
-    if target is None or prior is None:
-        raise UnsupportedByEngine("ControlledLangevinSDE.target_score / prior_score must be bound Distribution.score methods")
-    desc.target = dist_desc(target, device, keep)
-    desc.prior = dist_desc(prior, device, keep)
-    desc.cmcd_g = scalar_of(sde.diff_coeff)
-    desc.cmcd_clip = scalar_of(sde.clip_score) if sde.clip_score else 0.0
     rows = _RowArrays(_f32c(xs).view(M * B, d))
     if desc.target.kind in R.GRAPHLESS_TARGETS and score_ext is None:
-        _, score_ext = dist_eval(target, rows.x, want_logp=False, want_score=True)
+        _, score_ext = dist_eval(_self_of(sde.target_score), rows.x, want_logp=False, want_score=True)
     if score_ext is not None:
         score_ext = _f32c(score_ext)
         if tuple(score_ext.shape) != (M * B, d):
             raise ValueError(f"cmcd_kl_adjoint: score_ext {tuple(score_ext.shape)}, want {(M * B, d)}")
-    cf = _f32c(coef.to(device=device))
-    desc.coef = cf.data_ptr()
     cb = _f32c(cbar)
     lam0 = torch.empty(B, d, dtype=torch.float32, device=device)
     wv, ln = _f32c(w).view(B), _f32c(lam_n)
@@ -1009,8 +1046,7 @@ def ctrl_forward(ctrl, t: float, x: torch.Tensor, score_gain=1.0, lerp_w=0.0):
     require_gpu(x)
     lib = L.lib()
     device, keep = x.device, []
-    desc = L.Desc()
-    desc.abi_version = L.ABI_VERSION
+    desc = new_desc()
     desc.net = net_desc(ctrl, device, keep)
     tgt, prior = ctrl_target(ctrl)
     desc.target = dist_desc(tgt, device, keep)
@@ -1168,6 +1204,15 @@ def _tilted_workspace(net, d, need, device):
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
 
 
+def _tilted_run(net, d, need, launch, device):
+    """Launch into ``d`` with the net's workspace of ``need`` bytes; ``need`` 0 means the size query rejected the descriptor: one launch
+    without a workspace fetches the code and the reason."""
+    if need == 0:
+        _check_supported(launch())
+    _tilted_workspace(net, d, need, device)
+    _check_supported(launch())
+
+
 def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
     """The one launch behind tilted_eval (sdeng_tilted_eval) and tilted_vjp (``train``: sdeng_tilted_vjp, with the per-row arrays)."""
     require_gpu(x)
@@ -1195,10 +1240,7 @@ def _tilted_launch(net, t, x, want_grad, want_logp, per_row_times, train):
     else:
         launch = lambda: lib.sdeng_tilted_eval(C.byref(d), _stream_ptr(device))  # noqa: E731
         need = lib.sdeng_tilted_eval_workspace_bytes(C.byref(d))
-    if need == 0:
-        _check_supported(launch())  # the descriptor is rejected: fetch the code and the reason
-    _tilted_workspace(net, d, need, device)
-    _check_supported(launch())
+    _tilted_run(net, d, need, launch, device)
     return logp, grad, arrays, (n_times, B, tdev[:, 0])
 
 
@@ -1246,12 +1288,8 @@ def tilted_moves(net, t, x, lp, grad, step, n_moves, *, keep_from=0, unadjusted=
     mv.x, mv.lp, mv.grad, mv.step = x.data_ptr(), lp.data_ptr(), grad.data_ptr(), step.data_ptr()
     mv.z, mv.u, mv.seed, mv.chain0 = _ptr(z), _ptr(u), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain0)
     mv.samples, mv.acc_sum, mv.acc_last = _ptr(samples), _ptr(acc), _ptr(last)
-    launch = lambda: lib.sdeng_tilted_moves(C.byref(d), C.byref(mv), _stream_ptr(device))  # noqa: E731
-    need = lib.sdeng_tilted_moves_workspace_bytes(C.byref(d))
-    if need == 0:
-        _check_supported(launch())  # the descriptor is rejected: fetch the code and the reason
-    _tilted_workspace(net, d, need, device)
-    _check_supported(launch())
+    _tilted_run(net, d, lib.sdeng_tilted_moves_workspace_bytes(C.byref(d)),
+                lambda: lib.sdeng_tilted_moves(C.byref(d), C.byref(mv), _stream_ptr(device)), device)
     return samples, acc, last
 
 
@@ -1301,12 +1339,8 @@ def tilted_simulate(net, ctrl, coef: torch.Tensor, tinfo: torch.Tensor, x: torch
             raise ValueError(f"tilted_simulate: noise must be [N,B,d] = {(N, B, dim)}, got {tuple(nz.shape)}")
     run.x_in, run.noise_in, run.x_out, run.rnd_out = xin.data_ptr(), _ptr(nz), x_out.data_ptr(), rnd.data_ptr()
     run.xs_out, run.ref_out = _ptr(xs), _ptr(ref)
-    launch = lambda: lib.sdeng_tilted_simulate(C.byref(d), C.byref(run), _stream_ptr(device))  # noqa: E731
-    need = lib.sdeng_tilted_simulate_workspace_bytes(C.byref(d), C.byref(run))
-    if need == 0:
-        _check_supported(launch())  # the descriptors are rejected: fetch the code and the reason
-    _tilted_workspace(net, d, need, device)
-    _check_supported(launch())
+    _tilted_run(net, d, lib.sdeng_tilted_simulate_workspace_bytes(C.byref(d), C.byref(run)),
+                lambda: lib.sdeng_tilted_simulate(C.byref(d), C.byref(run), _stream_ptr(device)), device)
     return x_out, rnd, xs, ref
 
 

@@ -13,15 +13,24 @@ SURVEY.md 8f-2) is a HIP launch too (RDS losses, DiscreteTimeReversalLossEI, CMC
 from the discrete adjoint of the step loop for the KL methods (``_kl_loss``, ``_kl_loss_cmcd``).  What those calls share -- the rollout, the KL
 weights, the parameter gradients from a kernel's per-row arrays, the hand-off to autograd, the adjoints themselves -- is ``losses/training.py``.
 
+Each class states its step loop ONCE, in ``_step_loop`` (-> ``StepLoop``: form, flags, table options, reference, whether the initial log-density
+enters and the EMA control is honoured); ``simulate``, ``eval``, ``compute_eubo`` and the training call hand that declaration to ``_launch``, which
+takes seed and control perturbation as arguments and returns, next to (x_N, rnd, xs), the record of what it ran (``engine.Launched``: declaration,
+device table, compiled net / reference / lerp prior).  The gradient code reads lin, ito, table and reference from that record: it differentiates
+the recursion the kernel integrated.  (The parts are compiled before the launch's own checks, so where several refusals apply to one call the
+table's or the control's may now come before the RemoveReferenceCtrl / terminal / initial-density ones; each refusal is unchanged.)
+
 Extra, engine-only knobs (keyword-only, default to the reference behaviour):
   * ``noise=[N,B,d]`` injects the normals (replays the reference's ``randn_like`` stream, parity mode);
     without it the kernel draws counter-based Philox normals keyed by ``self.seed`` and the global
-    particle index ``self.particle0 + row`` (independent of how the batch is sharded over GPUs).
+    particle index ``self.particle0 + row`` (independent of how the batch is sharded over GPUs);
+  * ``call`` (``simulate`` only; INTERNAL to the training calls, ``training.launch_call``): a training call's seed and perturbation in, the
+    launch's record out (``call.ran``) -- arguments of that one call, where the loss object used to be written to.  Leave it unset.
 """
 from __future__ import annotations
 
 import logging
-from typing import Callable
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -34,10 +43,24 @@ from . import training as T
 from .training import _capturable, _FusedIntegral, _GraphedAdjointStep, _graphed_step, _IntegralPass, ctrl_batched, fused_net_view, fused_training_ok, vjp_param_grads  # noqa: F401  (all stay reachable here)
 
 
+class StepLoop(NamedTuple):
+    """A loss class's declaration of its step loop for one direction (``_step_loop``); the gradient code reads it back from ``engine.Launched.decl``."""
+    form: int                   # L.FORM_*
+    flags: int                  # L.FLAG_ITO, or 0 (CMCD: its three flags)
+    coef_kw: dict               # table kind (default: the class's ``kind``) and options of ``_coef``
+    ref: tuple = ("none", {})   # the resolved reference drift
+    ref_ctrl: object = None     # the same as the callable the torch adjoints differentiate (None without a reference drift)
+    init: bool = True           # does the initial log-density enter (dropped for KL training in the DIS family)
+    ema: bool = True            # is ``use_ema`` honoured
+    lin = property(lambda self: self.form == L.FORM_LIN)
+    ito = property(lambda self: bool(self.flags & L.FLAG_ITO))
+
+
 class BaseOCLoss:
     """Mirror of losses/oc.py:14-200."""
 
     kind = None  # coefficient-table kind of the subclass
+    optional_ito = False  # does simulate() take ``compute_ito_int`` (eval() then asks for the Ito integral only with the weights)
 
     def __init__(self, generative_ctrl: Callable, generative_ctrl_ema: Callable, sde=None, method: str = "kl",
                  traj_per_sample: int = 1, filter_samples: Callable | None = None, max_rnd: float | None = None,
@@ -75,7 +98,6 @@ class BaseOCLoss:
         self._graphed = {}
         self.split_tiles = False  # True: small batches (<= _lib.SPLIT_TILES_MAX_B = 8 192, the library's own gate) ask for the low-latency kernels (SDENG_FLAG_SPLIT_TILES; fp32-round-off, not bit, equal to the standard kernel); the solvers switch it on (cfg 'split_tiles', default True)
         self.dist = None  # torch.distributed of a sharded run: eval() then returns global estimators and globally normalised weights
-        self._perturb = {}  # coefficient-table options of the control perturbation, set for the step loop of a log-variance training call
         self._nn_times = None  # an energy-based ('nn') reference: (coefficient table, net, its time table [N, 5] on the device) of the last grid
 
     # ---- reference surface -----------------------------------------------------------------
@@ -161,6 +183,14 @@ class BaseOCLoss:
             metrics["eval/norm_effective_sample_size"] = host[3].item()  # eval/metrics.py:135-140
         return make_results(samples=samples, weights=w, log_norm_const_preds=preds, ts=ts, xs=xs, metrics=metrics)
 
+    def eval(self, ts, x, terminal_unnorm_log_prob, reference_log_prob=None, compute_weights=True, return_traj=True,
+             use_ema=True, *, noise=None) -> Results:
+        """eval() of the losses that end in ``reference_log_prob`` (the DIS / CMCD families start from ``initial_log_prob``: _InitialLogProbLoss)."""
+        kw = dict(compute_ito_int=compute_weights) if self.optional_ito else {}
+        samples, rnd, xs = self.simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
+                                         change_sde_ctrl=False, return_traj=return_traj, use_ema=use_ema, noise=noise, **kw)
+        return BaseOCLoss.compute_results(rnd, compute_weights=compute_weights, ts=ts, samples=samples, xs=xs, dist=self.dist)
+
     def __call__(self, ts, x, *args, **kwargs):
         raise E.UnsupportedByEngine(
             f"{type(self).__name__} has no training call: the subclasses implement loss(ts, x, ...) for the log-variance methods "
@@ -172,10 +202,23 @@ class BaseOCLoss:
     def state_dict(self) -> dict:
         return {"n_filtered": self.n_filtered}
 
-    def _lv_loss(self, ts, x, simulate, *, coef_kw=None, rnd0=None, ito=True):
+    def _train(self, ts, x, terminal_unnorm_log_prob, sim_kw, rnd0=None):
+        """The training call of the FORM_LIN / FORM_EM losses: the step loop is ``simulate(**sim_kw)`` with the trajectory kept, handed the call's
+        seed and perturbation by ``training.rollout`` (``call``).  It never adds the initial log-density: log-variance training adds ``rnd0``."""
+        reference_log_prob = sim_kw.get("reference_log_prob")
+
+        def launch(xx, call):
+            return self.simulate(ts, xx, terminal_unnorm_log_prob, return_traj=True, call=call, **sim_kw)
+        if self.method not in ("kl", "kl_ito"):
+            return self._lv_loss(ts, x, launch, rnd0=rnd0)
+        if reference_log_prob is None:
+            return self._kl_loss(ts, x, launch, lambda xn: -terminal_unnorm_log_prob(xn).view(-1, 1))
+        return self._kl_loss(ts, x, launch, lambda xn: reference_log_prob(xn).view(-1, 1) - terminal_unnorm_log_prob(xn).view(-1, 1))
+
+    def _lv_loss(self, ts, x, launch, *, rnd0=None):
         """Log-variance training value (losses/oc.py ``__call__`` of every loss, method in ('lv', 'lv_traj')).  The
         trajectories are driven by the DETACHED control (generative_and_sde_ctrl, :83-103), so the states carry no graph
-        and the step loop is exactly the eval path: it runs as one HIP launch (``simulate(x)`` with the trajectory kept) and its log-weights ARE the loss's
+        and the step loop is exactly the eval path: it runs as one HIP launch (``launch(x)`` with the trajectory kept) and its log-weights ARE the loss's
             rnd = rnd0 + sum_k c_k <u_k, u_k.detach() - u_k/2> + c'_k <u_k, z_k> + terminal(x_N);
         their gradient comes from ONE batched pass of the control over all N*B (time, state) pairs
         (:269-271, :284 EM; :490-491, :499 EI / DDPM-like; :957-958, :965 DIS; :1361-1383 DDS).  KL training differentiates
@@ -184,11 +227,9 @@ class BaseOCLoss:
         # sde_ctrl_noise / sde_ctrl_dropout (generative_and_sde_ctrl, :97-102): the step loop perturbs the control it integrates with --
         # the perturbed control then IS the control of every term of the value (the reference writes it in place through the detached
         # alias), while the gradient below is unchanged: c'_k z_k back through the net, along the perturbed trajectory
-        perturb = self._ctrl_perturbation()
-        coef_kw = dict(coef_kw or {}, **perturb)
         # VALUE: the step loop already integrates exactly this rnd (the detached control is the control), terminal terms included.  (the kernel draws the normals
         # of stream seed_c itself -- bit for bit the z below -- so small batches may take the low-latency split-tile kernel, which does not replay noise)
-        x, x_n, rnd_sim, xs, seed_c, N, B, d = T.rollout(self, ts, x, simulate, perturb=perturb)
+        x, x_n, rnd_sim, xs, ran, seed_c, N, B, d = T.rollout(self, ts, x, launch, perturb=self._ctrl_perturbation())
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)
         with torch.no_grad():
             rnd_val = rnd_sim.reshape(B, 1)
@@ -198,8 +239,8 @@ class BaseOCLoss:
         # u.detach() = u (in fp32 too: (u - u/2) - u/2 = 0 exactly, which is what the reference's autograd produces).  So the only
         # part of rnd that needs a graph is the stochastic integral s_b = sum_k c'_k <u_kb, z_kb>, from one batched pass of the
         # control; it enters with value zero (s - s.detach()), and compute_loss / backward() do the rest as upstream.
-        coef = self._coef(ts, x.device, **coef_kw)  # coef[:, 0]: the net's time of step k, coef[:, 5]: c'_k (the step loop's own table)
-        zc = (z.view(N, B, d) * (coef[:, 5] if ito else torch.zeros_like(coef[:, 5])).view(N, 1, 1)).view(N * B, d)
+        coef = ran.coef  # coef[:, 0]: the net's time of step k, coef[:, 5]: c'_k (the table the step loop ran on)
+        zc = (z.view(N, B, d) * coef[:, 5].view(N, 1, 1)).view(N * B, d)
         s = self._integral_pass(coef[:, 0].contiguous(), xs[:-1], zc)
         return self.compute_loss(rnd_val + (s - s.detach()).view(B, 1), samples=x_n)
 
@@ -242,7 +283,7 @@ class BaseOCLoss:
             self._graphed[key] = fn
         return fn(t_unique, xs.contiguous(), zc)
 
-    def _kl_loss(self, ts, x, simulate, terminal, *, lin, coef_kw=None, reference_ctrl=None, ito=True):
+    def _kl_loss(self, ts, x, launch, terminal):
         """KL training value and gradient (``method in ('kl', 'kl_ito')``): loss = mean of the log-weights over the particles that pass
         ``filter``, differentiated THROUGH the trajectory (BaseOCLoss.compute_loss losses/oc.py:105-131 on ``simulate(change_sde_ctrl=
         False)``, where the control that drives the SDE is the un-detached control: :258-260, :478-484, :1361-1365).
@@ -258,22 +299,21 @@ class BaseOCLoss:
         reference's ``loss.backward()`` produces (fixtures ``train_kl_*``: loss to 6 digits, gradients to fp32 round-off)."""
         if self.sde_ctrl_noise is not None or self.sde_ctrl_dropout is not None:
             raise E.UnsupportedByEngine("sde_ctrl_noise / sde_ctrl_dropout perturb the simulated control (losses/oc.py:97-101): not built")
-        x, x_n, rnd_sim, xs, seed_c, N, B, d = T.rollout(self, ts, x, simulate)
+        x, x_n, rnd_sim, xs, ran, seed_c, N, B, d = T.rollout(self, ts, x, launch)
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)  # bit for bit the normals the kernel drew
         _, w, value = T.kl_weights(self, rnd_sim.reshape(B, 1), x_n)
         ctrl = self.generative_ctrl
         params = [p for p in ctrl.parameters() if p.requires_grad]
-        coef = self._coef(ts, x.device, **(coef_kw or {}))
         with torch.enable_grad():
             xN = x_n.detach().requires_grad_(True)
             lam, = torch.autograd.grad((w * terminal(xN).view(B, 1)).sum(), xN)
-        self.last_adjoint_path = R.kl_route(self, reference_ctrl)
+        self.last_adjoint_path = R.kl_route(self, ran.decl.ref_ctrl)
         if self.last_adjoint_path == "native":
-            grads = T.kl_grads_native(ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, ref_kind=E.resolve_reference(reference_ctrl))
+            grads = T.kl_grads_native(ctrl, params, ran, xs, z, w, lam)
         elif self.last_adjoint_path == "fused":
-            grads = T.kl_grads_fused(ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, reference_ctrl=reference_ctrl)
+            grads = T.kl_grads_fused(ctrl, params, ran, xs, z, w, lam)
         else:
-            grads = T.kl_grads_stepwise(self, ctrl, params, coef, xs, z, w, lam, lin=lin, ito=ito, reference_ctrl=reference_ctrl)
+            grads = T.kl_grads_stepwise(self, ctrl, params, ran, xs, z, w, lam)
         return T.hand_to_autograd(self, value, params, grads)
 
     # ---- engine plumbing ---------------------------------------------------------------------
@@ -382,26 +422,29 @@ class BaseOCLoss:
             rnd += term
         return rnd
 
-    def _simulate(self, ts, x, *, terminal_unnorm_log_prob, reference_log_prob=None, initial_log_prob=None, form,
-                  flags, use_ema, return_traj, noise, ref=("none", {}), coef_kw=None):
+    def _launch(self, loop, ts, x, *, terminal_unnorm_log_prob, reference_log_prob=None, initial_log_prob=None, use_ema=False, return_traj=False,
+                noise=None, seed=None, perturb=None):
+        """The step loop ``loop`` (a ``StepLoop``) as one launch -> (x_N, rnd, xs or None, ``engine.Launched``: what it ran on).  ``seed``: the Philox
+        stream (default: the eval stream ``self.seed``); ``perturb``: ``_ctrl_perturbation()`` of a log-variance training call."""
         E.require_gpu(x)
+        form, ref = loop.form, loop.ref
+        seed = int(self.seed if seed is None else seed)
+        coef_kw = dict(loop.coef_kw, **(perturb or {}))
+        ctrl = self._ctrl(use_ema and loop.ema)
         if ref[0] == "nn":  # an energy-based reference: the step loop of sdeng_tilted_simulate
-            return self._simulate_nn(ts, x, ref[1]["net"], terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                                     initial_log_prob=initial_log_prob, form=form, flags=flags, use_ema=use_ema, return_traj=return_traj,
-                                     noise=noise, coef_kw=coef_kw)
+            return self._launch_nn(loop, ts, x, ctrl, coef_kw, terminal_unnorm_log_prob, reference_log_prob, initial_log_prob, return_traj, noise, seed,
+                                   perturb)
         if isinstance(x, E.InitialDraw) and (form == L.FORM_EUBO or (initial_log_prob is not None and E.resolve_logp(initial_log_prob) is None)):
-            x = self._x0(x)  # an opaque initial log-density needs x0 as a tensor; the noising loops start from data anyway
+            x = self._x0(x, seed)  # an opaque initial log-density needs x0 as a tensor; the noising loops start from data anyway
         device = x.device
-        keep = []
-        desc = L.Desc()
+        ran = E.compile_ctrl(ctrl, self._coef(ts, device, **coef_kw), device, ref, decl=loop)
+        keep, desc = ran.keep, E.new_desc()
         desc.form = form
-        desc.flags = flags | (L.FLAG_SPLIT_TILES if self.split_tiles and x.shape[0] <= L.SPLIT_TILES_MAX_B else 0)
         desc.N = ts.numel() - 1
-        desc.seed = int(self.seed)
+        desc.seed = seed
         desc.particle0 = int(self.particle0)
-        ctrl = self._ctrl(use_ema)
-        desc.net = E.net_desc(ctrl, device, keep)
-        desc.ref = E.ref_desc(ref[0], ref[1], device, keep)
+        desc.flags = loop.flags | (L.FLAG_SPLIT_TILES if self.split_tiles and x.shape[0] <= L.SPLIT_TILES_MAX_B else 0)
+        desc.net, desc.ref, desc.prior, desc.coef = ran.net, ran.ref, ran.prior, ran.coef.data_ptr()  # (the prior slot: a LerpCtrl's prior, SDENG_DIST_NONE without one, unless the kernel adds the initial log-density)
         _, remove = E.unwrap_ctrl(ctrl)
         if remove is not None:  # RemoveReferenceCtrl: u = ctrl - ref_score, with the reference score the step loop already evaluates
             if ref[0] == "none" or not E.same_reference(E.resolve_reference(remove.ref_score)[1], ref[1]):
@@ -412,7 +455,6 @@ class BaseOCLoss:
         if desc.target.kind == L.DIST_GMM_FULL and (ref[0] != "none" or form == L.FORM_EUBO):
             raise E.UnsupportedByEngine("a full-covariance mixture target inside a Score / Lerp / CancelDrift control is evaluated in the kernel's "
                                         "reference slot: forward passes of the solvers without a reference drift (PIS / DDS / DIS) only")
-        desc.prior = E.dist_desc(E.ctrl_target(ctrl)[1], device, keep)  # a LerpCtrl's prior (SDENG_DIST_NONE without one), unless the kernel adds the initial log-density
         rnd0 = None
         if initial_log_prob is not None:
             pr = E.resolve_logp(initial_log_prob)
@@ -423,12 +465,8 @@ class BaseOCLoss:
                 desc.flags |= L.FLAG_INIT_LOGP
             except E.UnsupportedByEngine:
                 rnd0 = initial_log_prob if form == L.FORM_EUBO else initial_log_prob(x).view((-1, 1))  # EUBO: at the noised samples
-        if self._perturb:  # log-variance training with sde_ctrl_noise / sde_ctrl_dropout (BaseOCLoss._lv_loss)
-            coef_kw = dict(coef_kw or {}, **self._perturb)
-            desc.flags |= (L.FLAG_CTRL_NOISE if "ctrl_noise" in self._perturb else 0) | (L.FLAG_CTRL_DROPOUT if "ctrl_dropout" in self._perturb else 0)
-        coef = self._coef(ts, device, **(coef_kw or {}))
-        keep.append(coef)
-        desc.coef = coef.data_ptr()
+        if perturb:  # log-variance training with sde_ctrl_noise / sde_ctrl_dropout (BaseOCLoss._lv_loss)
+            desc.flags |= (L.FLAG_CTRL_NOISE if "ctrl_noise" in perturb else 0) | (L.FLAG_CTRL_DROPOUT if "ctrl_dropout" in perturb else 0)
         x_out, rnd, xs = E.run(desc, x, keep, return_traj=return_traj, noise=noise, events=self.timing_events)
         if callable(rnd0):
             rnd0 = rnd0(x_out).view((-1, 1))
@@ -436,9 +474,16 @@ class BaseOCLoss:
             rnd += rnd0
         rnd = self._apply_late(rnd, x if form == L.FORM_EUBO else x_out, late)  # EUBO: the cost at the data, x_in
         assert rnd.shape == (x.shape[0], 1)
-        return x_out, rnd, xs
+        return x_out, rnd, xs, ran
 
-    def _nn_refusal(self, ctrl, form=None):
+    def _run(self, loop, ts, x, call, **kw):
+        """simulate()'s launch -> (x_N, rnd, xs).  ``call`` is internal to the training calls (``training.launch_call``; None for every other
+        caller): it carries a training call's seed and perturbation in and the launch's record out (``call.ran``)."""
+        call = call or T.launch_call()
+        *out, call.ran = self._launch(loop, ts, x, seed=call.seed, perturb=call.perturb, **kw)
+        return tuple(out)
+
+    def _nn_refusal(self, ctrl, form=None, perturb=None):
         """Why this loss cannot run over an energy-based ('nn') reference -- the reason, in words -- or None.  The kernel of
         sdeng_tilted_simulate holds the reference score and a ClippedCtrl; everything that would need the reference score inside the
         control, a perturbed control or the noising direction has no kernel there."""
@@ -448,19 +493,18 @@ class BaseOCLoss:
         if rec.kind != L.CTRL_CLIPPED:
             return (f"{R.name_of(rec.ctrl)} over an energy-based ('nn') reference: the one-launch step loop holds a ClippedCtrl only "
                     "(Score / Lerp / CancelDrift controls need the target score next to the EBM walk)")
-        if self.sde_ctrl_noise is not None or self.sde_ctrl_dropout is not None or self._perturb:
+        if self.sde_ctrl_noise is not None or self.sde_ctrl_dropout is not None or perturb:
             return "sde_ctrl_noise / sde_ctrl_dropout over an energy-based ('nn') reference: the kernel has no control-perturbation stage"
         if form == L.FORM_EUBO:
             return "compute_eubo over an energy-based ('nn') reference: no noising loop is built around the EBM walk"
         return None
 
-    def _simulate_nn(self, ts, x, net, *, terminal_unnorm_log_prob, reference_log_prob, initial_log_prob, form, flags, use_ema, return_traj,
-                     noise, coef_kw):
-        """``_simulate`` over an energy-based reference (RDS.change_reference_type('nn'), solver/oc.py:577-585): one
+    def _launch_nn(self, loop, ts, x, ctrl, coef_kw, terminal_unnorm_log_prob, reference_log_prob, initial_log_prob, return_traj, noise, seed, perturb):
+        """``_launch`` over an energy-based reference (RDS.change_reference_type('nn'), solver/oc.py:577-585): one
         sdeng_tilted_simulate launch for the N steps, then the terminal costs with the launches that exist -- ``reference_log_prob``
         (WrapperDistrNN.log_prob: sdeng_tilted_eval at eps) and the target's log-density (sdeng_dist_eval) -- as losses/oc.py:290, :505, :645."""
-        ctrl = self._ctrl(use_ema)
-        why = self._nn_refusal(ctrl, form)
+        net, form = loop.ref[1]["net"], loop.form
+        why = self._nn_refusal(ctrl, form, perturb)
         if why is None and initial_log_prob is not None:
             why = "an initial log-density over an energy-based ('nn') reference: the RDS losses have none"
         if why is None:
@@ -468,13 +512,13 @@ class BaseOCLoss:
             why = why and f"energy-based ('nn') reference: {why}"
         if why is not None:
             raise E.UnsupportedByEngine(why)
-        x = self._x0(x)
-        coef = self._coef(ts, x.device, **(coef_kw or {}))
+        x = self._x0(x, seed)
+        coef = self._coef(ts, x.device, **coef_kw)
         hit = self._nn_times
         if hit is None or hit[0] is not coef or hit[1] is not net:  # the reference's times of this grid: read back once per table
             t_net = coef[:, 0].detach().to("cpu")
             hit = self._nn_times = (coef, net, E.tilted_times(net, t_net, t_net.numel(), per_row=True)[2].to(x.device))
-        x_out, rnd, xs, _ = E.tilted_simulate(net, ctrl, coef, hit[2], x, form=form, flags=flags & L.FLAG_ITO, seed=int(self.seed),
+        x_out, rnd, xs, _ = E.tilted_simulate(net, ctrl, coef, hit[2], x, form=form, flags=loop.flags & L.FLAG_ITO, seed=seed,
                                               particle0=int(self.particle0), noise=noise, return_traj=return_traj)
         term = 0.0  # rnd += reference_log_prob(x) - terminal_unnorm_log_prob(x): the difference first, as upstream
         if reference_log_prob is not None:
@@ -483,7 +527,7 @@ class BaseOCLoss:
             term = term - self._logp(terminal_unnorm_log_prob, x_out)
         rnd += term
         assert rnd.shape == (x.shape[0], 1)
-        return x_out, rnd, xs
+        return x_out, rnd, xs, E.Launched(coef, None, None, decl=loop)  # (log-variance training reads the table; no adjoint runs over an EBM)
 
     def _no_train(self, change_sde_ctrl):
         if change_sde_ctrl:
@@ -502,56 +546,43 @@ class EMReferenceSDELoss(BaseOCLoss):
         self.reference_ctrl = reference_ctrl
         self.use_rescaling = use_rescaling
 
-    def simulate(self, ts, x, terminal_unnorm_log_prob, reference_log_prob, change_sde_ctrl=False, return_traj=False,
-                 use_ema=False, *, noise=None):
-        self._no_train(change_sde_ctrl)
+    def _step_loop(self, train=False, ito=True, eubo=False, dim=None):
+        ref = E.resolve_reference(self.reference_ctrl)
+        if eubo:
+            return StepLoop(L.FORM_EUBO, 0, dict(with_ref=True, kind="eubo_ei" if self.kind == "ei" else "eubo_em", rescale=bool(self.use_rescaling)), ref)
         if not self.use_rescaling and type(self) is EMReferenceSDELoss:
             raise E.UnsupportedByEngine("EMReferenceSDELoss(use_rescaling=False) scales the control twice upstream "
                                         "(losses/oc.py:265-267); not reproduced")
-        ref = E.resolve_reference(self.reference_ctrl)
-        return self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                              form=L.FORM_EM if self.kind == "em" else L.FORM_LIN, flags=L.FLAG_ITO, use_ema=use_ema,
-                              return_traj=return_traj, noise=noise, ref=ref, coef_kw=dict(with_ref=ref[0] != "none"))
+        with_ref = ref[0] != "none"  # (the Ito term is always part of these losses, :284, :499)
+        return StepLoop(L.FORM_EM if self.kind == "em" else L.FORM_LIN, L.FLAG_ITO, dict(with_ref=with_ref), ref, self.reference_ctrl if with_ref else None)
+
+    def simulate(self, ts, x, terminal_unnorm_log_prob, reference_log_prob, change_sde_ctrl=False, return_traj=False,
+                 use_ema=False, *, noise=None, call=None):
+        self._no_train(change_sde_ctrl)
+        return self._run(self._step_loop(), ts, x, call, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
+                         use_ema=use_ema, return_traj=return_traj, noise=noise)
 
     def __call__(self, ts, x, terminal_unnorm_log_prob, reference_log_prob):
-        """[TRAINING] losses/oc.py:364-394 (see BaseOCLoss._lv_loss)."""
-        def sim(xx):
-            return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                                 change_sde_ctrl=False, return_traj=True, use_ema=False)
-        ref_kind = E.resolve_reference(self.reference_ctrl)[0]
-        with_ref = ref_kind != "none"
-        if ref_kind == "nn":  # an energy-based reference: log-variance training of a ClippedCtrl only, refused before any rollout
+        """[TRAINING] losses/oc.py:364-394 with change_sde_ctrl = False (see BaseOCLoss._train)."""
+        if E.resolve_reference(self.reference_ctrl)[0] == "nn":  # an energy-based reference: log-variance training of a ClippedCtrl only, refused before any rollout
             why = R.KL_OVER_NN if self.method in ("kl", "kl_ito") else self._nn_refusal(self.generative_ctrl)
             if why is not None:
                 raise E.UnsupportedByEngine(why)
-        if self.method in ("kl", "kl_ito"):  # :364-394 with change_sde_ctrl = False; the Ito term is always part of these losses (:284, :499)
-            return self._kl_loss(ts, x, sim,
-                                 lambda xn: reference_log_prob(xn).view(-1, 1) - terminal_unnorm_log_prob(xn).view(-1, 1),
-                                 lin=self.kind != "em", coef_kw=dict(with_ref=with_ref), reference_ctrl=self.reference_ctrl if with_ref else None)
-        return self._lv_loss(ts, x, sim, coef_kw=dict(with_ref=with_ref))
+        return self._train(ts, x, terminal_unnorm_log_prob, dict(reference_log_prob=reference_log_prob))
 
     def compute_eubo(self, ts, x, terminal_unnorm_log_prob, reference_log_prob, use_ema=False, *, noise=None):
         """losses/oc.py:298-362 (EM; inherited by the DDPM-like loss) and :512-568 (EI): noising trajectories started at
         target samples ``x`` and the density log-ratio along them, as ONE HIP launch (SDENG_FORM_EUBO).  Like the
         reference, ``x`` is noised in place."""
-        ref = E.resolve_reference(self.reference_ctrl)
-        if ref[0] == "none":
+        loop = self._step_loop(eubo=True)
+        if loop.ref[0] == "none":
             raise E.UnsupportedByEngine("compute_eubo needs a reference control (RDS losses)")
-        if ref[0] == "nn":
+        if loop.ref[0] == "nn":
             raise E.UnsupportedByEngine(R.KL_OVER_NN if self.method in ("kl", "kl_ito") else self._nn_refusal(self._ctrl(use_ema), L.FORM_EUBO))
-        kind = "eubo_ei" if self.kind == "ei" else "eubo_em"
-        x_out, rnd, _ = self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                                       form=L.FORM_EUBO, flags=0, use_ema=use_ema, return_traj=False, noise=noise, ref=ref,
-                                       coef_kw=dict(with_ref=True, kind=kind, rescale=bool(self.use_rescaling)))
+        x_out, rnd, _, _ = self._launch(loop, ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
+                                        use_ema=use_ema, noise=noise)
         x.copy_(x_out)
         return rnd
-
-    def eval(self, ts, x, terminal_unnorm_log_prob, reference_log_prob=None, compute_weights=True, return_traj=True,
-             use_ema=True, *, noise=None) -> Results:
-        samples, rnd, xs = self.simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob,
-                                         reference_log_prob=reference_log_prob, change_sde_ctrl=False,
-                                         return_traj=return_traj, use_ema=use_ema, noise=noise)
-        return BaseOCLoss.compute_results(rnd, compute_weights=compute_weights, ts=ts, samples=samples, xs=xs, dist=self.dist)
 
 
 class EIReferenceSDELoss(EMReferenceSDELoss):
@@ -584,10 +615,9 @@ class _InitialLogProbLoss(BaseOCLoss):
 
     def eval(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, compute_weights=True, return_traj=True,
              use_ema=True, *, noise=None) -> Results:
-        kw = dict(compute_ito_int=compute_weights) if isinstance(self, TimeReversalLoss) else {}
-        samples, rnd, xs = self.simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob,
-                                         initial_log_prob=initial_log_prob, train=False, return_traj=return_traj,
-                                         use_ema=use_ema, noise=noise, **kw)
+        kw = dict(compute_ito_int=compute_weights) if self.optional_ito else {}
+        samples, rnd, xs = self.simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False,
+                                         return_traj=return_traj, use_ema=use_ema, noise=noise, **kw)
         return BaseOCLoss.compute_results(rnd, compute_weights=compute_weights, ts=ts, samples=samples, xs=xs, dist=self.dist)
 
 
@@ -600,43 +630,37 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         super().__init__(*args, **kwargs)
         self.use_rescaling = use_rescaling
 
-    def simulate(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, train=True, change_sde_ctrl=False,
-                 return_traj=False, use_ema=False, *, noise=None, eubo=False):
-        self._no_train(change_sde_ctrl)
-        if train and self.method in ["kl", "kl_ito"]:
-            raise E.UnsupportedByEngine("CMCD KL-training start (rnd0 = 0) is part of the training direction")
+    def _step_loop(self, train=False, ito=True, eubo=False, dim=None):
         if not self.use_rescaling:
             raise E.UnsupportedByEngine("ControlledLangevinSDELoss(use_rescaling=False) scales the control twice upstream "
                                         "(losses/oc.py:716-719); not reproduced")
+        return StepLoop(L.FORM_CMCD_EUBO if eubo else L.FORM_CMCD, L.FLAG_ITO | L.FLAG_INIT_LOGP | L.FLAG_TERM_TARGET, dict(kind="cmcd_eubo") if eubo else {})
+
+    def _launch(self, loop, ts, x, *, terminal_unnorm_log_prob, initial_log_prob=None, use_ema=False, return_traj=False, noise=None, seed=None, perturb=None):
+        """CMCD's step loop (the kernel adds the initial log-density and the terminal target itself) -> (x_N, rnd, xs or None, what it ran on)."""
         E.require_gpu(x)
-        if eubo:
-            x = self._x0(x)
-        device = x.device
-        keep = []
-        desc = L.Desc()
-        desc.form = L.FORM_CMCD_EUBO if eubo else L.FORM_CMCD
-        desc.flags = L.FLAG_ITO | L.FLAG_INIT_LOGP | L.FLAG_TERM_TARGET
-        desc.N = ts.numel() - 1
-        desc.seed, desc.particle0 = int(self.seed), int(self.particle0)
-        desc.net = E.net_desc(self._ctrl(use_ema), device, keep)
-        target, prior = R.self_of(self.sde.target_score), R.self_of(self.sde.prior_score)
-        if target is None or prior is None:
-            raise E.UnsupportedByEngine("ControlledLangevinSDE.target_score / prior_score must be bound Distribution.score methods")
+        seed = int(self.seed if seed is None else seed)
+        if loop.form == L.FORM_CMCD_EUBO:
+            x = self._x0(x, seed)
+        desc, ran = E.cmcd_desc(self._ctrl(use_ema), self.sde, self._coef(ts, x.device, **loop.coef_kw), x.device, loop.form, decl=loop)
         res = E.resolve_logp(terminal_unnorm_log_prob)
-        if res is None or res[0] is not target:
+        if res is None or res[0] is not R.self_of(self.sde.target_score):
             raise E.UnsupportedByEngine("CMCD: terminal_unnorm_log_prob must be the log-density of sde.target_score's distribution")
         pr = E.resolve_logp(initial_log_prob) if initial_log_prob is not None else None
-        if pr is None or pr[0] is not prior:
+        if pr is None or pr[0] is not R.self_of(self.sde.prior_score):
             raise E.UnsupportedByEngine("CMCD: initial_log_prob must be the log-density of sde.prior_score's distribution")
-        desc.target = E.dist_desc(target, device, keep, clip=res[1])
-        desc.prior = E.dist_desc(prior, device, keep)
-        desc.cmcd_g = E.scalar_of(self.sde.diff_coeff)
-        desc.cmcd_clip = E.scalar_of(self.sde.clip_score) if self.sde.clip_score else 0.0
-        coef = self._coef(ts, device, kind="cmcd_eubo") if eubo else self._coef(ts, device)
-        keep.append(coef)
-        desc.coef = coef.data_ptr()
-        x_out, rnd, xs = E.run(desc, x, keep, return_traj=return_traj, noise=noise, events=self.timing_events)
-        return x_out, rnd, xs
+        desc.target.clip = float(res[1]) if res[1] else 0.0  # (clipped_target_unnorm_log_prob, solver/oc.py:80-87: the terminal term's, not the adjoint's)
+        desc.flags, desc.N = loop.flags, ts.numel() - 1
+        desc.seed, desc.particle0 = seed, int(self.particle0)
+        return E.run(desc, x, ran.keep, return_traj=return_traj, noise=noise, events=self.timing_events) + (ran,)
+
+    def simulate(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, train=True, change_sde_ctrl=False,
+                 return_traj=False, use_ema=False, *, noise=None, eubo=False, call=None):
+        self._no_train(change_sde_ctrl)
+        if train and self.method in ["kl", "kl_ito"]:
+            raise E.UnsupportedByEngine("CMCD KL-training start (rnd0 = 0) is part of the training direction")
+        return self._run(self._step_loop(eubo=eubo), ts, x, call, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=initial_log_prob,
+                         use_ema=use_ema, return_traj=return_traj, noise=noise)
 
     def compute_eubo(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, use_ema=False, *, noise=None):
         """losses/oc.py:757-828: the CMCD loop run from target samples with the control subtracted, one HIP launch
@@ -657,13 +681,14 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
             raise E.UnsupportedByEngine("sde_ctrl_noise / sde_ctrl_dropout perturb the simulated control: not built")
         if self.method in ("kl", "kl_ito"):
             return self._kl_loss_cmcd(ts, x, terminal_unnorm_log_prob, initial_log_prob)
-        x, _, _, _, seed_c, N, B, d = T.rollout(self, ts, x)  # (the step loop below replays the injected z on the eval stream: no seed swap)
+        x, _, _, _, _, seed_c, N, B, d = T.rollout(self, ts, x)  # (the step loop below replays the injected z on the eval stream: no seed in its call)
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)
         g = float(self.sde.diff_coeff)
+        call = T.launch_call()
         with torch.no_grad():
             x_n, _, xs = self.simulate(ts, x, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False,
-                                       return_traj=True, use_ema=False, noise=z)
-            b_all, _ = self._cmcd_drifts(self._coef(ts, x.device), xs)  # eq/sdes.py:101-110 at every (ts[j], xs[j])
+                                       return_traj=True, use_ema=False, noise=z, call=call)
+            b_all, _ = self._cmcd_drifts(call.ran.coef, xs)  # eq/sdes.py:101-110 at every (ts[j], xs[j]); the table the step loop ran on
             b_s, b_t = b_all[:-1], b_all[1:]
             const = -terminal_unnorm_log_prob(x_n)
             if initial_log_prob is not None:
@@ -720,8 +745,8 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         (``last_adjoint_path`` 'native'), else one torch vector-Jacobian product per step ('stepwise': two control evaluations share the
         state y, so the step is differentiated as a whole; the target / prior scores are differentiated exactly where the reference's are:
         closed-form scores carry a graph, autograd-made ones do not, distr/base.py:146-154).  The shared pieces: losses/training.py."""
-        x, x_n, rnd_sim, xs, seed_c, N, B, d = T.rollout(self, ts, x, lambda xx: self.simulate(
-            ts, xx, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False, return_traj=True))
+        x, x_n, rnd_sim, xs, ran, seed_c, N, B, d = T.rollout(self, ts, x, lambda xx, call: self.simulate(
+            ts, xx, terminal_unnorm_log_prob, initial_log_prob=initial_log_prob, train=False, return_traj=True, call=call))
         z = E.philox_noise(seed_c, N, B, d, self.particle0, x.device)  # bit for bit the normals the kernel drew
         _, w, value = T.kl_weights(self, rnd_sim.reshape(B, 1) - self._logp(initial_log_prob, x), x_n)  # (the evaluation pass starts from log p_prior(x0), training from 0)
         ctrl = self.generative_ctrl
@@ -737,11 +762,11 @@ class ControlledLangevinSDELoss(_InitialLogProbLoss):
         self.last_adjoint_path = R.cmcd_kl_route(self)
         if self.last_adjoint_path == "native":
             # the kernel's input, the per-step cost cotangents, is one batched forward pass over the HIP states; parameter gradients as in _kl_loss
-            coef = self._coef(ts, x.device)
+            coef = ran.coef
             with torch.no_grad():
                 cbar, s_tgt = self._cmcd_step_costs(ctrl, coef, xs, z)
             graphless = R.dist_kind(R.self_of(self.sde.target_score)) in R.GRAPHLESS_TARGETS
-            arrays, _ = E.cmcd_kl_adjoint(ctrl, self.sde, coef, xs, cbar, w, lam, score_ext=s_tgt if graphless else None)
+            arrays, _ = E.cmcd_kl_adjoint(ctrl, self.sde, coef, xs, cbar, w, lam, score_ext=s_tgt if graphless else None, parts=ran)
             return T.hand_to_autograd(self, value, params, T.param_grads(ctrl, coef[:, 0].contiguous(), arrays, N + 1, B, params))
         grads = [torch.zeros_like(p) for p in params]
 
@@ -776,30 +801,29 @@ class DiscreteTimeReversalLossEI(_InitialLogProbLoss):
         super().__init__(*args, **kwargs)
         self.use_rescaling = False
 
+    def _step_loop(self, train=False, ito=True, eubo=False, dim=None):
+        if eubo:
+            return StepLoop(L.FORM_EUBO, 0, dict(kind="eubo_ei"))
+        return StepLoop(L.FORM_LIN, L.FLAG_ITO, {}, init=not (train and self.method in ("kl", "kl_ito")))  # rnd0 = 0 for the KL methods (:935-939)
+
     def simulate(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, train=True, change_sde_ctrl=False,
-                 return_traj=False, use_ema=False, *, noise=None):
+                 return_traj=False, use_ema=False, *, noise=None, call=None):
         self._no_train(change_sde_ctrl)
-        init = None if (train and self.method in ["kl", "kl_ito"]) else initial_log_prob
-        return self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=init,
-                              form=L.FORM_LIN, flags=L.FLAG_ITO, use_ema=use_ema, return_traj=return_traj, noise=noise)
+        loop = self._step_loop(train)
+        return self._run(loop, ts, x, call, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=initial_log_prob if loop.init else None,
+                         use_ema=use_ema, return_traj=return_traj, noise=noise)
 
     def __call__(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None):
-        """[TRAINING] losses/oc.py:1038-1066, log-variance methods (rnd0 = log p_prior(x0), terminal -log pi~)."""
-        def sim(xx):
-            return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=None, train=True,
-                                 change_sde_ctrl=False, return_traj=True, use_ema=False)
-        if self.method in ("kl", "kl_ito"):  # :1038-1066; rnd0 = 0 for the KL methods (:935-939)
-            return self._kl_loss(ts, x, sim, lambda xn: -terminal_unnorm_log_prob(xn).view(-1, 1), lin=True)
-        return self._lv_loss(ts, x, sim, rnd0=initial_log_prob)
+        """[TRAINING] losses/oc.py:1038-1066 (log-variance: rnd0 = log p_prior(x0); terminal -log pi~)."""
+        return self._train(ts, x, terminal_unnorm_log_prob, {}, rnd0=initial_log_prob)
 
     def compute_eubo(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, use_ema=False, *, noise=None):
         """losses/oc.py:980-1036: noising trajectories from target samples (no reference; cost 0.5|u|^2 omega, Ito term,
         + log p_prior of the noised samples), one HIP launch.  ``x`` is noised in place like upstream."""
         if initial_log_prob is None:
             raise ValueError("compute_eubo needs initial_log_prob (the reference calls it unconditionally, losses/oc.py:1032)")
-        x_out, rnd, _ = self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=initial_log_prob,
-                                       form=L.FORM_EUBO, flags=0, use_ema=use_ema, return_traj=False, noise=noise,
-                                       coef_kw=dict(kind="eubo_ei"))
+        x_out, rnd, _, _ = self._launch(self._step_loop(eubo=True), ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob,
+                                        initial_log_prob=initial_log_prob, use_ema=use_ema, noise=noise)
         x.copy_(x_out)
         return rnd
 
@@ -808,6 +832,7 @@ class TimeReversalLoss(_InitialLogProbLoss):
     """losses/oc.py:1105-1307 (original DIS, without inference control)."""
 
     kind = "time_reversal"
+    optional_ito = True
 
     def __init__(self, *args, inference_ctrl: Callable | None = None, div_estimator: str | None = None,
                  use_rescaling: bool = True, **kwargs):
@@ -816,67 +841,45 @@ class TimeReversalLoss(_InitialLogProbLoss):
             raise ValueError("use_rescaling must be True for TimeReversalLoss.")
         self.inference_ctrl, self.div_estimator, self.use_rescaling = inference_ctrl, div_estimator, use_rescaling
 
-    def simulate(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, train=True, compute_ito_int=False,
-                 change_sde_ctrl=False, return_traj=False, use_ema=False, *, noise=None):
-        self._no_train(change_sde_ctrl)
+    def _step_loop(self, train=False, ito=True, eubo=False, dim=None):
         if self.inference_ctrl is not None:
             raise E.UnsupportedByEngine("a learned inference control needs the divergence of a net (autograd): not on the HIP path")
-        init = None if (train and self.method in ["kl", "kl_ito"]) else initial_log_prob
         lerp = R.describe_ctrl(self.generative_ctrl).own_kind == L.CTRL_LERP
-        # quirk kept: TimeReversalLoss.simulate never uses the EMA net (losses/oc.py:1177-1180)
-        return self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=init,
-                              form=L.FORM_EM, flags=L.FLAG_ITO if compute_ito_int else 0, use_ema=False,
-                              return_traj=return_traj, noise=noise, coef_kw=dict(train=train, dim=x.shape[-1], lerp=lerp))
+        # ema=False: quirk kept, TimeReversalLoss.simulate never uses the EMA net (losses/oc.py:1177-1180)
+        return StepLoop(L.FORM_EM, L.FLAG_ITO if ito else 0, dict(train=train, dim=dim, lerp=lerp),
+                        init=not (train and self.method in ("kl", "kl_ito")), ema=False)
+
+    def simulate(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None, train=True, compute_ito_int=False,
+                 change_sde_ctrl=False, return_traj=False, use_ema=False, *, noise=None, call=None):
+        self._no_train(change_sde_ctrl)
+        loop = self._step_loop(train, compute_ito_int, dim=x.shape[-1])
+        return self._run(loop, ts, x, call, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=initial_log_prob if loop.init else None,
+                         use_ema=use_ema, return_traj=return_traj, noise=noise)
 
     def __call__(self, ts, x, terminal_unnorm_log_prob, initial_log_prob=None):
-        """[TRAINING] losses/oc.py:1240-1272, log-variance methods, no inference control: cost <u, u.detach() - u/2> dt + <u, db>."""
-        lerp = R.describe_ctrl(self.generative_ctrl).own_kind == L.CTRL_LERP
-        kl = self.method in ("kl", "kl_ito")
-        ito = self.method != "kl"  # :1251 compute_ito_int = self.method != "kl"
-
-        def sim(xx):
-            return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, initial_log_prob=None, train=True,
-                                 compute_ito_int=ito, change_sde_ctrl=False, return_traj=True, use_ema=False)
-        if kl:
-            if self.inference_ctrl is not None:
-                raise E.UnsupportedByEngine("a learned inference control needs the divergence of a net (autograd): not on the HIP path")
-            return self._kl_loss(ts, x, sim, lambda xn: -terminal_unnorm_log_prob(xn).view(-1, 1), lin=False,
-                                 coef_kw=dict(train=True, dim=x.shape[-1], lerp=lerp), ito=ito)
-        return self._lv_loss(ts, x, sim, rnd0=initial_log_prob, coef_kw=dict(train=True, dim=x.shape[-1], lerp=lerp))
+        """[TRAINING] losses/oc.py:1240-1272, no inference control: cost <u, u.detach() - u/2> dt + <u, db>; :1251 compute_ito_int = self.method != "kl"."""
+        return self._train(ts, x, terminal_unnorm_log_prob, dict(compute_ito_int=self.method != "kl"), rnd0=initial_log_prob)
 
 
 class ExponentialIntegratorSDELoss(BaseOCLoss):
     """losses/oc.py:1310-1467 (DDS)."""
 
     kind = "dds"
+    optional_ito = True
 
     def __init__(self, *args, alpha: float, sigma: float, **kwargs):
         super().__init__(*args, **kwargs)
         self.alpha, self.sigma = alpha, sigma
 
+    def _step_loop(self, train=False, ito=True, eubo=False, dim=None):
+        return StepLoop(L.FORM_LIN, L.FLAG_ITO if ito else 0, dict(alpha=self.alpha, sigma=self.sigma))
+
     def simulate(self, ts, x, terminal_unnorm_log_prob, reference_log_prob, compute_ito_int=False, change_sde_ctrl=False,
-                 return_traj=False, use_ema=False, *, noise=None):
+                 return_traj=False, use_ema=False, *, noise=None, call=None):
         self._no_train(change_sde_ctrl)
-        return self._simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                              form=L.FORM_LIN, flags=L.FLAG_ITO if compute_ito_int else 0, use_ema=use_ema,
-                              return_traj=return_traj, noise=noise, coef_kw=dict(alpha=self.alpha, sigma=self.sigma))
+        return self._run(self._step_loop(ito=compute_ito_int), ts, x, call, terminal_unnorm_log_prob=terminal_unnorm_log_prob,
+                         reference_log_prob=reference_log_prob, use_ema=use_ema, return_traj=return_traj, noise=noise)
 
     def __call__(self, ts, x, terminal_unnorm_log_prob, reference_log_prob):
-        """[TRAINING] losses/oc.py:1399-1428, log-variance methods (compute_ito_int = True for them)."""
-        ito = self.method != "kl"  # :1414 compute_ito_int = self.method != "kl"
-
-        def sim(xx):
-            return self.simulate(ts, xx, terminal_unnorm_log_prob=terminal_unnorm_log_prob, reference_log_prob=reference_log_prob,
-                                 compute_ito_int=ito, change_sde_ctrl=False, return_traj=True, use_ema=False)
-        if self.method in ("kl", "kl_ito"):
-            return self._kl_loss(ts, x, sim,
-                                 lambda xn: reference_log_prob(xn).view(-1, 1) - terminal_unnorm_log_prob(xn).view(-1, 1), lin=True,
-                                 coef_kw=dict(alpha=self.alpha, sigma=self.sigma), ito=ito)
-        return self._lv_loss(ts, x, sim, coef_kw=dict(alpha=self.alpha, sigma=self.sigma))
-
-    def eval(self, ts, x, terminal_unnorm_log_prob, reference_log_prob=None, compute_weights=True, return_traj=True,
-             use_ema=True, *, noise=None) -> Results:
-        samples, rnd, xs = self.simulate(ts, x, terminal_unnorm_log_prob=terminal_unnorm_log_prob,
-                                         reference_log_prob=reference_log_prob, compute_ito_int=compute_weights,
-                                         change_sde_ctrl=False, return_traj=return_traj, use_ema=use_ema, noise=noise)
-        return BaseOCLoss.compute_results(rnd, compute_weights=compute_weights, ts=ts, samples=samples, xs=xs, dist=self.dist)
+        """[TRAINING] losses/oc.py:1399-1428; :1414 compute_ito_int = self.method != "kl"."""
+        return self._train(ts, x, terminal_unnorm_log_prob, dict(reference_log_prob=reference_log_prob, compute_ito_int=self.method != "kl"))

@@ -3,6 +3,8 @@ log-variance training (``ctrl_batched``, ``_IntegralPass``, the fused ``_FusedIn
 a training kernel's per-row arrays, the hand-off to autograd, the three adjoints of ``_kl_loss`` and the graph-captured per-step runner."""
 from __future__ import annotations
 
+import types
+
 import torch
 
 from .. import _lib as L
@@ -128,12 +130,19 @@ class _IntegralPass(torch.nn.Module):
 
 
 # ---- the pieces every training call shares -----------------------------------------------------------------------------------------
+def launch_call(seed=None, perturb=None):
+    """The internal ``call`` argument of the losses' ``simulate``: a training call's Philox seed and perturbation options in (None: the eval
+    stream, no perturbation), the launch's record out (``ran``: ``engine.Launched``)."""
+    return types.SimpleNamespace(seed=seed, perturb=perturb, ran=None)
+
+
 def rollout(loss, ts, x, simulate=None, perturb=None):
     """The front of every training call: one fresh Philox stream (the reference consumes torch's global generator; call c here uses seed + c *
     golden-ratio increment for the step noise AND for an x0 left to the engine, call 0 being the eval stream of ``seed``), x0 as a tensor, the
-    ``traj_per_sample`` repeat.  With ``simulate`` (a callable of x0) the HIP step loop runs on that stream (``loss.seed`` swapped, ``loss._perturb``
-    set for a perturbed log-variance call, both restored whatever happens); a caller that needs the normals the kernel drew redraws them bit for
-    bit with ``E.philox_noise(seed_c, N, B, d, loss.particle0, x.device)``.  -> (x, x_n, rnd_sim, xs, seed_c, N, B, d)."""
+    ``traj_per_sample`` repeat.  With ``simulate`` (a callable of x0 and ``call``) the HIP step loop runs on that stream and with the table options
+    ``perturb`` of a perturbed log-variance call -- both travel as the argument ``call``, which comes back holding the launch's record ``ran``
+    (``engine.Launched``); a caller that needs the kernel's normals redraws them bit for bit with ``E.philox_noise(seed_c, N, B, d,
+    loss.particle0, x.device)``.  -> (x, x_n, rnd_sim, xs, ran, seed_c, N, B, d)."""
     E.require_gpu(x)
     seed_c = loss._next_train_seed()
     x = loss._x0(x, seed_c)
@@ -141,16 +150,11 @@ def rollout(loss, ts, x, simulate=None, perturb=None):
         x = x.repeat(loss.traj_per_sample, 1, 1).reshape(-1, x.shape[-1])
     N, (B, d) = ts.numel() - 1, x.shape
     x_n = rnd_sim = xs = None
+    call = launch_call(seed_c, perturb)
     if simulate is not None:
-        seed_eval, loss.seed = loss.seed, seed_c
-        loss._perturb = perturb or {}
-        try:
-            with torch.no_grad():
-                x_n, rnd_sim, xs = simulate(x)
-        finally:
-            loss.seed = seed_eval
-            loss._perturb = {}
-    return x, x_n, rnd_sim, xs, seed_c, N, B, d
+        with torch.no_grad():
+            x_n, rnd_sim, xs = simulate(x, call)
+    return x, x_n, rnd_sim, xs, call.ran, seed_c, N, B, d
 
 
 def kl_weights(loss, rnd_val, x_n):
@@ -210,18 +214,21 @@ def walk_adjoint(loss, key, step, grads, lam, rest, N, graph):
 
 
 # ---- the three adjoints of BaseOCLoss._kl_loss: each -> the gradients, ordered as ``params`` -------------------------------------------------
-def kl_grads_native(ctrl, params, coef, xs, z, w, lam, *, lin, ito, ref_kind):
+def kl_grads_native(ctrl, params, ran, xs, z, w, lam):
     """A control ``routes.kl_native`` accepts, no / a diagonal reference: the whole recursion is ONE launch (sdeng_kl_adjoint: lambda in registers, u
-    recomputed, closed-form Hessian-vector products); the parameter gradients come from the per-row arrays, as in log-variance training."""
+    recomputed, closed-form Hessian-vector products) over the parts the step loop's launch compiled; the parameter gradients come from the
+    per-row arrays, as in log-variance training."""
+    coef, lin, ito = ran.coef, ran.decl.lin, ran.decl.ito
     N, B = xs.shape[0] - 1, xs.shape[1]
-    arrays, _ = E.kl_adjoint(ctrl, coef, xs[:-1], z if ito else None, w, lam, lin=lin, ito=ito, ref=ref_kind)
+    arrays, _ = E.kl_adjoint(ctrl, coef, xs[:-1], z if ito else None, w, lam, lin=lin, ito=ito, parts=ran)
     return param_grads(ctrl, coef[:, 0].contiguous(), arrays, N, B, params)
 
 
-def kl_grads_fused(ctrl, params, coef, xs, z, w, lam, *, lin, ito, reference_ctrl):
+def kl_grads_fused(ctrl, params, ran, xs, z, w, lam):
     """ClippedCtrl over the FourierMLP with a reference the one-launch kernel does not differentiate: the control's part of each step's
     vector-Jacobian product is the fused HIP forward + backward of that time step (sdeng_ctrl_vjp; weights packed once per call), the
     reference score's part a small torch VJP; the parameter gradients come from the per-row arrays at the end."""
+    coef, lin, ito, reference_ctrl = ran.coef, ran.decl.lin, ran.decl.ito, ran.decl.ref_ctrl
     N, B = xs.shape[0] - 1, xs.shape[1]
     sess = E.VjpSession(ctrl, coef[:, 0], xs[:-1])
     u_all = sess.forward_u()
@@ -244,9 +251,10 @@ def kl_grads_fused(ctrl, params, coef, xs, z, w, lam, *, lin, ito, reference_ctr
     return param_grads(ctrl, coef[:, 0].contiguous(), sess.arrays(), N, B, params)
 
 
-def kl_grads_stepwise(loss, ctrl, params, coef, xs, z, w, lam, *, lin, ito, reference_ctrl):
+def kl_grads_stepwise(loss, ctrl, params, ran, xs, z, w, lam):
     """Every other control / target / reference: one torch vector-Jacobian product of the kernel's own step per SDE step (FORM_LIN / FORM_EM
     with the host's per-step coefficients, include/sdeng.h), the HIP states as constants."""
+    coef, lin, ito, reference_ctrl = ran.coef, ran.decl.lin, ran.decl.ito, ran.decl.ref_ctrl
     grads = [torch.zeros_like(p) for p in params]
 
     def step(lam_in, x_in, z_in, c, w_in):

@@ -39,22 +39,21 @@ def time_steps(mode):
 
 
 def time_loop(mode):
-    """The step-loop launch of a training call alone (BaseOCLoss._lv_loss sets the table options for its simulate)."""
+    """The step-loop launch of a training call alone (BaseOCLoss._lv_loss hands the table options to its launch)."""
     set_mode(mode)
     x = model.prior.sample((B,)).to(model.device)
-    loss._perturb = loss._ctrl_perturbation()
-    try:
-        for _ in range(3):
-            with torch.no_grad():
-                loss.simulate(model.train_ts, x, model.clipped_target_unnorm_log_prob, model.reference_distr.log_prob, return_traj=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(STEPS):
-            with torch.no_grad():
-                loss.simulate(model.train_ts, x, model.clipped_target_unnorm_log_prob, model.reference_distr.log_prob, return_traj=True)
-        torch.cuda.synchronize()
-    finally:
-        loss._perturb = {}
+
+    def launch():
+        with torch.no_grad():
+            loss._launch(loss._step_loop(train=True), model.train_ts, x, terminal_unnorm_log_prob=model.clipped_target_unnorm_log_prob,
+                         reference_log_prob=model.reference_distr.log_prob, return_traj=True, perturb=loss._ctrl_perturbation())
+    for _ in range(3):
+        launch()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(STEPS):
+        launch()
+    torch.cuda.synchronize()
     return (time.perf_counter() - t0) / STEPS
 
 
